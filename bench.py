@@ -14,6 +14,12 @@ N-GPU job renders the 1080p frame at 64*N spp. The partitions are gathered to
 rank 0 over RCCL (torch.distributed, backend nccl) at the end of every step.
 
 value = rays traced by all ranks / max-over-ranks wall time of the K steps.
+
+A plain run sets up, warms up, times the K steps (`--steps K`), writes the
+last step's frame if `--dump-outputs DIR` is given and prints the result line.
+`--full` adds everything else: the oracle parity frame, the counted step
+(roofline, valu, work), the one-lane step, the CPU baseline, the secondary
+configs and, on N > 1 GPUs, the strong-scaling C4 frame.
 """
 import argparse
 import json
@@ -333,6 +339,33 @@ def strong_c4(pkg, rank, world, backend, own_comm, threads, frames=2):
     return rec
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: the files written (arrays and .npy headers) stay within this
+NPY_HEADER_BYTES = 256   # room kept per file for its .npy header (128 bytes for these shapes)
+
+
+def dump_outputs(path, acc, cnt):
+    """--dump-outputs: the frame a caller of the timed path receives, acc
+    (H, W, 3) radiance sums and cnt (H, W) samples per pixel, as
+    radiance.npy (float32) and sample_count.npy (float64). A frame over
+    DUMP_BYTES is cut to a fixed seeded sample of its pixels, whose flat
+    indices y * W + x go to pixel_index.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    acc = np.ascontiguousarray(acc, dtype=np.float32)
+    cnt = np.asarray(cnt).astype(np.float64)
+    index = os.path.join(path, "pixel_index.npy")
+    if os.path.exists(index):
+        os.remove(index)  # of an earlier, sampled dump into the same directory
+    if acc.nbytes + cnt.nbytes + 2 * NPY_HEADER_BYTES > DUMP_BYTES:
+        k = (DUMP_BYTES - 3 * NPY_HEADER_BYTES) // (3 * 4 + 8 + 8)  # radiance, count and index bytes of a pixel
+        pix = np.sort(np.random.default_rng(0x5EED).choice(cnt.size, size=k, replace=False))
+        acc, cnt = acc.reshape(-1, 3)[pix], cnt.reshape(-1)[pix]
+        np.save(index, pix.astype(np.float64))
+    np.save(os.path.join(path, "radiance.npy"), acc)
+    np.save(os.path.join(path, "sample_count.npy"), cnt)
+
+
 def _free_port():
     import socket
 
@@ -400,6 +433,15 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--spp", type=int, default=0, help="override spp per GPU share (testing only)")
     ap.add_argument("--batch", type=int, default=1 << 27, help="paths resident per wavefront batch (2^27: one C3 step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: the "
+                         "oracle parity frame, the counted step (roofline, work), the one-lane step, the CPU "
+                         "baseline, the secondary configs and (N>1) the strong-scaling C4 frame; the --no-* "
+                         "options below drop single parts of it. Without --full only the timed steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what a caller of the timed path receives after the last "
+                         "step (rank 0's frame: radiance.npy float32 (H, W, 3), sample_count.npy float64 (H, W)) "
+                         "to DIR; a frame over 64 MB is cut to a fixed seeded pixel sample (pixel_index.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serial-step", action="store_true", help="skip the one-lane step (standalone kernel times)")
     ap.add_argument("--no-secondary", action="store_true",
@@ -420,8 +462,9 @@ def main():
                     help="N>1 with RCCL: the product's communicator (wpt_set_comm / wpt_gather_frame) or "
                          "torch.distributed (multigpu.FrameGather)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
-    import numpy as np
     import torch
     import torch.distributed as dist
     import wpt_loader
@@ -521,7 +564,8 @@ def main():
 
     def do_gather():
         """Every rank's partition into rank 0's frame; returns rank 0's frame
-        (H, W, 3) when `want` is set by the caller (parity), else None."""
+        (H, W, 4: radiance and the count's bits) from the torch.distributed
+        gather, else None (the product's gather leaves it in rank 0's session)."""
         t0 = time.perf_counter()
         frame = None
         if own_comm:
@@ -545,8 +589,7 @@ def main():
 
     def step():
         itf.compute(paths_per_step)
-        if world > 1:
-            do_gather()
+        return do_gather() if world > 1 else None
 
     for _ in range(args.warmup):
         step()
@@ -558,7 +601,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_frame = step()
     itf.sync()
     torch.cuda.synchronize()
     if world > 1:
@@ -568,10 +611,99 @@ def main():
     st = itf.stats()
     kt = itf.kernel_times()
     rays_local = st["rays"] + st["shadow_rays"]
+    gather_ms_per_step = gather_s[0] / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after the last timed step:
+        # the accumulated frame of the warm-up and timed steps (N > 1: the
+        # frame gathered to rank 0), before anything below resets it
+        if last_frame is None:
+            out_acc, out_cnt = itf.read_radiance(W, H)
+        else:
+            fr = last_frame.cpu().numpy()  # float4 per pixel: radiance, sample count as u32 bits
+            out_acc, out_cnt = fr[..., :3], fr[..., 3].view("uint32")
+        dump_outputs(args.dump_outputs, out_acc, out_cnt)
+    if world > 1:
+        rdev = "cuda" if args.backend == "nccl" else "cpu"
+        t = torch.tensor([dt], dtype=torch.float64, device=rdev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+        r = torch.tensor([rays_local], dtype=torch.float64, device=rdev)
+        dist.all_reduce(r, op=dist.ReduceOp.SUM)
+        rays_total = float(r.item())
+    else:
+        rays_total = float(rays_local)
+    trav_name = TRAVERSAL_NAMES.get(scene_trav, str(scene_trav))
+    total_kernel_ms = sum(v["busy_ms"] for v in kt.values())
+    strong = exchange is not None or args.scaling == "strong"
+
+    result = {
+        "metric": "Mray/s (primary+shadow+bounce) at 1920x1080, 1/2/4/8 GPU; L2 vs CPU ref",
+        "value": rays_total / dt / 1e6,
+        "unit": "Mray/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": ("synthetic: seeded 100k-triangle cloud in mesh slot 1 (bunny2.obj absent), per-path xorshift32 streams"
+                 if cfg["mesh"] else "built-in scene geometry, per-path xorshift32 streams"),
+        "config": {
+            "workload": f"{args.config.upper()} {cfg['name']} (scene id {cfg['scene']}), {W}x{H}, "
+                        + (f"{cfg['spp']} spp budget over {world} GPUs (strong), depth" if exchange is not None else
+                           f"{cfg['spp']} spp frame split over {world} GPUs (strong), depth" if strong else
+                           f"{cfg['spp']} spp per GPU share ({cfg['spp'] * world} spp frame), depth")
+                        + f" {cfg['depth']}, {('NoNEE', 'NormalNEE', 'PNEE')[cfg['nee']]}"
+                        f"{', adaptive' if cfg.get('adaptive') else ''}",
+            "paths_per_step_per_gpu": paths_per_step if exchange is None else paths_per_step / world,
+            "rays": int(rays_total),
+            "parallelism": (f"tile-partition x{world}" + (" (gloo rehearsal)" if args.backend != "nccl" else
+                                                          ", RCCL gather in libwpt.so" if own_comm else
+                                                          ", torch.distributed gather"
+                                                          + (f" (wpt_set_comm fell back: {comm_fallback})"
+                                                             if comm_fallback else "")))
+                           if world > 1 else "single GPU",
+        },
+        "scene_load": {"bvh2_build_ms": round(bvh_ms, 2), "bvh2_built_on": "gpu" if bvh_on_gpu else "host"},
+        "traversal": trav_name,
+        # busy = union of a kernel's launch intervals (lanes overlap, and
+        # different kernels of different lanes overlap each other too)
+        "kernel_share": {k: round(v["busy_ms"] / total_kernel_ms, 4) for k, v in kt.items()} if total_kernel_ms else {},
+        "kernel_busy_ms_per_step": {k: round(v["busy_ms"] / args.steps, 2) for k, v in kt.items()},
+        "kernel_launch_ms_per_step": {k: round(v["ms"] / args.steps, 2) for k, v in kt.items()},
+        "full": bool(args.full),
+    }
+    if world > 1:
+        result["gather_ms_per_step"] = gather_ms_per_step
+        result["render_ms_per_step"] = dt / args.steps * 1e3 - gather_ms_per_step
+    if args.full:
+        full_run(args, result, pkg, cfg, cloud, cam, rank, world, own_comm, paths_per_step, strong, st, kt,
+                 scene_trav, tri_scene, do_gather)
+    else:
+        itf.shutdown()
+    if rank == 0:
+        print(json.dumps(result))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_run(args, result, pkg, cfg, cloud, cam, rank, world, own_comm, paths_per_step, strong, st, kt,
+             scene_trav, tri_scene, do_gather):
+    """--full: everything the benchmark measures or checks besides the timed
+    steps, on main()'s open session (shut down here), added to `result`: the
+    oracle parity frame, the counted step (roofline, valu, work), the one-lane
+    step, the CPU baseline, the secondary configs and, N > 1, the C4 frame."""
+    import numpy as np
+
+    itf = pkg.interface
+    W, H = cfg["W"], cfg["H"]
+    rays_local = st["rays"] + st["shadow_rays"]
+    trav_name = result["traversal"]
     # the parity frame: one more PRODUCTION step (the timed kernels, work
     # counters off) after a reset, i.e. samples 0..spp-1 of every pixel of
     # this rank's partition, compared with the oracle's rows below
-    gather_ms_per_step = gather_s[0] / args.steps * 1e3
     gpu_acc = None
     if world == 1 and not cfg.get("adaptive"):
         itf.set_render_options(cfg["depth"], 0xBABABEBE, args.batch)  # resets the accumulation
@@ -597,7 +729,6 @@ def main():
     itf.compute(paths_per_step)
     itf.sync()
     stc = itf.stats()
-    photon_rays = st.get("photon_rays", 0)
     ktc = itf.kernel_times()
     itf.set_counting(False)
     # one more step with ONE lane: the kernels run serialised on the whole GPU
@@ -613,16 +744,6 @@ def main():
         itf.sync()
         kts = itf.kernel_times()
         itf.set_lanes(lanes_default)
-    if world > 1:
-        rdev = "cuda" if args.backend == "nccl" else "cpu"
-        t = torch.tensor([dt], dtype=torch.float64, device=rdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-        r = torch.tensor([rays_local], dtype=torch.float64, device=rdev)
-        dist.all_reduce(r, op=dist.ReduceOp.SUM)
-        rays_total = float(r.item())
-    else:
-        rays_total = float(rays_local)
 
     # Roofline of the dominant kernel: algorithmic bytes per launch / avg launch time.
     # extend: per ray 32 B (origin, dir) read + 8 B (t, id) written, node bytes
@@ -657,7 +778,6 @@ def main():
     # the traversal the scene runs (a scene without a BVH scans linearly in
     # the BVH2 kernels' instantiation)
     trav_id = 1 if scene_trav == 1 else 0
-    trav_name = TRAVERSAL_NAMES.get(scene_trav, str(scene_trav))
     kname = (f"k_{dom}<{'true' if tri_scene else 'false'}, false>" if dom == "trace" else
              f"k_{dom}<{'true' if tri_scene else 'false'}, false, {trav_id}>")
     if not args.traffic_csv:
@@ -696,41 +816,8 @@ def main():
             traffic_src = args.traffic_csv
         except Exception as e:  # noqa: BLE001
             traffic_src = f"unreadable: {e}"
-    total_kernel_ms = sum(v["busy_ms"] for v in kt.values())
-    strong = exchange is not None or args.scaling == "strong"
 
-    result = {
-        "metric": "Mray/s (primary+shadow+bounce) at 1920x1080, 1/2/4/8 GPU; L2 vs CPU ref",
-        "value": rays_total / dt / 1e6,
-        "unit": "Mray/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": ("synthetic: seeded 100k-triangle cloud in mesh slot 1 (bunny2.obj absent), per-path xorshift32 streams"
-                 if cfg["mesh"] else "built-in scene geometry, per-path xorshift32 streams"),
-        "config": {
-            "workload": f"{args.config.upper()} {cfg['name']} (scene id {cfg['scene']}), {W}x{H}, "
-                        + (f"{cfg['spp']} spp budget over {world} GPUs (strong), depth" if exchange is not None else
-                           f"{cfg['spp']} spp frame split over {world} GPUs (strong), depth" if strong else
-                           f"{cfg['spp']} spp per GPU share ({cfg['spp'] * world} spp frame), depth")
-                        + f" {cfg['depth']}, {('NoNEE', 'NormalNEE', 'PNEE')[cfg['nee']]}"
-                        f"{', adaptive' if cfg.get('adaptive') else ''}",
-            "paths_per_step_per_gpu": paths_per_step if exchange is None else paths_per_step / world,
-            "rays": int(rays_total),
-            "parallelism": (f"tile-partition x{world}" + (" (gloo rehearsal)" if args.backend != "nccl" else
-                                                          ", RCCL gather in libwpt.so" if own_comm else
-                                                          ", torch.distributed gather"
-                                                          + (f" (wpt_set_comm fell back: {comm_fallback})"
-                                                             if comm_fallback else "")))
-                           if world > 1 else "single GPU",
-        },
-        "scene_load": {"bvh2_build_ms": round(bvh_ms, 2), "bvh2_built_on": "gpu" if bvh_on_gpu else "host"},
-        "traversal": trav_name,
+    result.update({
         "roofline": {
             "bound": "hbm",
             "kernel": kname,
@@ -752,12 +839,7 @@ def main():
             "limiter": "latency of the dependent node -> primitive -> stack-pop loads at 8 waves/SIMD "
                        "(neither HBM nor VALU near peak; the BVH and primitives are L2/MALL-resident)",
         },
-        # busy = union of a kernel's launch intervals (lanes overlap, and
-        # different kernels of different lanes overlap each other too)
         "valu": valu,
-        "kernel_share": {k: round(v["busy_ms"] / total_kernel_ms, 4) for k, v in kt.items()} if total_kernel_ms else {},
-        "kernel_busy_ms_per_step": {k: round(v["busy_ms"] / args.steps, 2) for k, v in kt.items()},
-        "kernel_launch_ms_per_step": {k: round(v["ms"] / args.steps, 2) for k, v in kt.items()},
         # the same step with one lane (serialised kernels): standalone time per kernel, and the step
         "kernel_serial_ms_per_step": ({k: round(v["busy_ms"], 2) for k, v in kts.items() if v["busy_ms"] > 0}
                                       if kts else None),
@@ -779,10 +861,7 @@ def main():
                                        / max(stc["rays"] + stc["shadow_rays"], 1),
                  "expand_bodies_per_ray": stc["ex_bodies"] / max(stc["rays"] + stc["shadow_rays"], 1),
                  "leaf_bodies_per_ray": stc["lf_bodies"] / max(stc["rays"] + stc["shadow_rays"], 1)},
-    }
-    if world > 1:
-        result["gather_ms_per_step"] = gather_ms_per_step
-        result["render_ms_per_step"] = dt / args.steps * 1e3 - gather_ms_per_step
+    })
     if rank == 0 and not args.no_cpu_baseline:
         threads = args.cpu_threads or _host_threads()
         rec, rows, ref_rows = cpu_baseline(pkg, cfg, cloud, threads)
@@ -816,10 +895,6 @@ def main():
         t0 = time.perf_counter()
         result["secondary"] = secondary(pkg, args.cpu_threads or _host_threads())
         result["secondary_s"] = round(time.perf_counter() - t0, 1)
-    if rank == 0:
-        print(json.dumps(result))
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

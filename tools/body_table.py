@@ -19,8 +19,8 @@ tables) to the body of the traversal loop its source line belongs to:
 Instructions whose line lies in a header (ballot / popcount intrinsics) or
 carries no line (compiler-made moves) count for the body of the preceding
 attributed instruction. Counts are STATIC (every path through a body, its
-rare branches included). With a bench line (`--bench line.json`, from a run
-whose `work` block was counted) the table adds how often the loop runs each
+rare branches included). With a bench line (`--bench line.json`, from a
+`bench.py --full` run: its `work` block) the table adds how often the loop runs each
 body: wave-level executions per ray and lanes per execution (device ballots,
 `BodyLanes` in wpt_render.hip; extension and shadow walks together).
 

@@ -1,8 +1,8 @@
-"""Copy a tools/profile.sh run (gpurun_out/prof_<tag>) into profiles/<tag>/ and
+"""Copy a tools/profile.sh run (bench_out/prof_<tag>) into profiles/<tag>/ and
 write profiles/traffic_<config>.json, the per-launch HBM bytes bench.py reports
 as roofline.traffic for the same workload.
 
-Usage: python tools/collect_profile.py gpurun_out/prof_r01 r01 [config] [batch] [spp] [traversal] [lanes]
+Usage: python tools/collect_profile.py bench_out/prof_r01 r01 [config] [batch] [spp] [traversal] [lanes]
 (hbm_bytes_per_launch is per DISPATCH; bench.py scales it by the lanes of a logical launch;
 kernels are keyed by full instantiation, so the counting build's dispatches stay apart)
 """

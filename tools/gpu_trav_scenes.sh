@@ -3,7 +3,6 @@
 # (C5, museum), same session, plus C3.
 # Usage on the box: bash tools/gpu_trav_scenes.sh
 set -o pipefail
-mkdir -p gpurun_out
 B4=--opt=traversal=bvh4,--opt=traversal_sh=bvh4
 B2=--opt=traversal=bvh2,--opt=traversal_sh=bvh2
 AB_STEPS=${AB_STEPS:-3} AB_ARGS="--no-serial-step --no-secondary" bash tools/ab.sh c3=$B2 c5=--config=c5,$B2 c5b4=--config=c5,$B4 \

@@ -14,7 +14,7 @@ for spec in "$@"; do
   while read -r grp; do
     [ -z "$grp" ] && continue
     i=$((i+1))
-    timeout -s KILL 150 rocprofv3 --pmc $grp -d $OUT/p$i -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary $opts > $OUT/p$i.log 2>&1
+    timeout -s KILL 150 rocprofv3 --pmc $grp -d $OUT/p$i -o run --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary $opts > $OUT/p$i.log 2>&1
     rc=$?
     echo "$name pass $i rc=$rc"
     case $rc in 0) ;; *) echo "stopping after rc=$rc"; tail -3 $OUT/p$i.log; exit $rc;; esac

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 TAG=${1:-probe}
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline"
 timeout -s KILL 60 rocprofv3 --list-avail > $OUT/avail.txt 2>&1
 i=0
 while read -r grp; do

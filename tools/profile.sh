@@ -3,12 +3,12 @@
 #   kernel trace + stats, then separate --pmc passes (one counter group per pass,
 #   MI355X_MICROARCH.md §rocprofv3 PMC slots; FETCH_SIZE and WRITE_SIZE apart).
 # Default workload = bench.py's default (C3 1080p, 64 spp, depth 8), one step.
-# Usage: tools/profile.sh <tag> [bench args...]
+# Usage: tools/profile.sh <tag> [bench args...]   (writes to $OUT/prof_<tag>, OUT default bench_out)
 set -e
 TAG=${1:-r01}; shift || true
-ARGS=${@:-"--steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"}
+ARGS=${@:-"--full --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"}
 export TMPDIR=/tmp
-OUT=gpurun_out/prof_$TAG
+OUT=${OUT:-bench_out}/prof_$TAG
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $ARGS > $OUT/trace.log 2>&1
 i=0

@@ -3,7 +3,7 @@
 # summaries (the per-dispatch CSVs of a C5 step exceed gpurun's 64 MiB).
 export TMPDIR=/tmp
 O=gpurun_out/prof_c5small${1:+_$1}
-ARGS="--config c5 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"
+ARGS="--config c5 --full --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"
 mkdir -p $O /tmp/c5prof
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/c5prof/trace -o run --output-format csv -- python3 bench.py $ARGS > $O/trace.log 2>&1 || exit 1
 cp $(find /tmp/c5prof/trace -name "*kernel_stats.csv" | head -1) $O/c5_kernel_stats.csv

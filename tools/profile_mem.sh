@@ -3,7 +3,7 @@
 # workload. Usage: tools/profile_mem.sh <tag> [bench args...]
 set -e
 TAG=${1:-mem}; shift || true
-ARGS=${@:-"--steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"}
+ARGS=${@:-"--full --steps 1 --warmup 0 --no-cpu-baseline --no-serial-step --no-secondary"}
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
