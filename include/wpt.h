@@ -267,7 +267,9 @@ int wpt_seq_sum_device(const float* v, uint64_t n, float* out);
  * flight, out[36..37] = host microseconds in round planning and in the
  * stock's round step, out[38] = rays traced into the stock (extension +
  * shadow; rays and shadow rays count a stocked sample's when a round takes it),
- * out[39] = of rays + shadow rays, those of samples taken from the stock.
+ * out[39] = of rays + shadow rays, those of samples taken from the stock,
+ * out[40] = of rays, those their producer resolved (WPT_OPT_PRESOLVE: plane
+ * or miss, never fed to a traversal kernel; a stock refill's count when traced).
  * Visit/test/byte/iteration counts are only gathered with counting on. */
 int wpt_stats(uint64_t* out, size_t n);
 /* per-kernel device time (profiling on): out[0..11] = {ms, launches} ×
@@ -332,6 +334,9 @@ int wpt_set_lanes(int32_t n);
                                     counts, sized to the call's budget (default 1) */
 #define WPT_OPT_ASYNC_FUSED_BELOW 36 /* async batches (stock refills, filler) below this many paths run the fused k_trace
                                       (0: WPT_OPT_FUSED_BELOW; default 2^26) */
+#define WPT_OPT_PRESOLVE 37      /* 1 (default): k_generate / k_shade resolve extension rays that provably end on a plane or
+                                    in the background (exact root and guard box tests) and keep them out of the traversal
+                                    kernels' streams; 0: every ray is traversed. Depth-capped batches on BVH scenes only. */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -344,7 +349,9 @@ int wpt_set_option(int32_t option, int64_t value);
  * 5 fused trace), lane, bounce, waves, first entry} and rec[4e..4e+3] =
  * {start, the moment the wave's work feed ran dry, end, rays taken} per wave
  * entry e (steady-clock ticks, ticks_per_us of them per microsecond), then
- * restarts the recording. Call it first with meta = rec = NULL (the size
+ * restarts the recording. With WPT_OPT_PRESOLVE the rays of the bounce that
+ * their producer resolved, which no wave takes, are added to the launch's
+ * first entry. Call it first with meta = rec = NULL (the size
  * query: it takes the snapshot and sets *rec_entries to the entries rec must
  * hold), then with buffers: *rec_entries = rec's capacity in entries, meta
  * of 5 x the launches the query returned. */
@@ -366,6 +373,10 @@ int wpt_bvh_depth(void);
  * (Scene::shadow_ray, scene.rs:104-133) for {p.xyz, q.xyz} and light shape ids. */
 int wpt_trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out);
 int wpt_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occluded);
+/* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
+ * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
+ * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */
+int wpt_presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out);
 
 /* Tear the session down (the reference never does); allows a new wpt_init.
  * The sample stock's two ring blocks (about 42 GB at 1080p) stay with the
@@ -387,6 +398,12 @@ int wpt_debug_scene_nodes(void* h, uint32_t* out);
 /* 16 f32 per shape: geometry[12], kind, emissive, material rgb[...] packed as in wpt_scene.h */
 int wpt_debug_scene_shapes(void* h, float* out);
 int wpt_debug_scene_lights(void* h, uint32_t* out);
+/* The presolve's host restatement over the scene (as wpt_presolve_rays). */
+int wpt_debug_scene_presolve(void* h, size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out);
+/* Its guard boxes: *num_guards (0..4); boxes (may be NULL) = 30 f32: the BVH2
+ * root's bounds, then 4 guards (x_min,y_min,z_min,x_max,y_max,z_max);
+ * leaf_guard (may be NULL) = per BVH2 node the guard of a leaf, ~0 otherwise. */
+int wpt_debug_scene_guards(void* h, uint32_t* num_guards, float* boxes, uint32_t* leaf_guard);
 void wpt_debug_scene_free(void* h);
 /* The same scene with its BVH2 built on the GPU (the device of
  * wpt_set_device, default 0) whatever its size; same accessors. */

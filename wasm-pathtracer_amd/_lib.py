@@ -58,6 +58,9 @@ _SIGS = {
     "wpt_bvh_depth": (ctypes.c_int, []),
     "wpt_trace_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
     "wpt_shadow_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
+    "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
+    "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
+    "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),
     "wpt_shutdown": (ctypes.c_int, []),
     "wpt_debug_scene_new": (c_p, [c_i32, c_p, c_sz]),
     "wpt_debug_scene_info": (ctypes.c_int, [c_p, c_p]),

@@ -553,7 +553,7 @@ int wpt_stats(uint64_t* out, size_t n) {
   std::string err;
   if (!g_session->renderer.flush_counts(err)) return fail(WPT_ERR_DEVICE, err);
   const Stats& st = g_session->renderer.stats();
-  uint64_t v[40] = {st.paths,          st.rays,           st.shadow_rays,    st.node_visits,  st.prim_tests,
+  uint64_t v[41] = {st.paths,          st.rays,           st.shadow_rays,    st.node_visits,  st.prim_tests,
                     st.bounces,        st.ext_visits,     st.ext_tests,      st.ext_node_bytes, st.sh_visits,
                     st.sh_tests,       st.sh_node_bytes,  st.fallback_ext,   st.fallback_sh,  st.ext_lane_iters,
                     st.ext_live_iters, st.sh_lane_iters,  st.sh_live_iters,  st.photon_rays,  st.photons,
@@ -561,8 +561,8 @@ int wpt_stats(uint64_t* out, size_t n) {
                     st.trace_bytes,    st.finish_paths,   st.finish_max_bounces, st.max_ray_visits,
                     st.ex_body_lanes,  st.ex_bodies,      st.lf_body_lanes,  st.lf_bodies,    st.stock_traced,
                     st.stock_deficit,  st.stock_waits,    st.plan_us,        st.stock_us,
-                    st.stock_rays,     st.stock_rays_used};
-  for (size_t i = 0; i < n && i < 40; i++) out[i] = v[i];
+                    st.stock_rays,     st.stock_rays_used, st.presolved_rays};
+  for (size_t i = 0; i < n && i < 41; i++) out[i] = v[i];
   return WPT_OK;
 }
 
@@ -727,6 +727,14 @@ int wpt_trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out) {
   return WPT_OK;
 }
 
+int wpt_presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (n && (!rays || !resolved || !t_out || !id_out)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  std::string err;
+  if (!g_session->renderer.presolve_rays(n, rays, resolved, t_out, id_out, err)) return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 int wpt_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occluded) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   std::string err;
@@ -860,6 +868,43 @@ int wpt_debug_scene_lights(void* h, uint32_t* out) {
   const HostScene* sc = (const HostScene*)h;
   if (!sc) return fail(WPT_ERR_INVALID_ARG, "null scene");
   for (size_t i = 0; i < sc->lights.size(); i++) out[i] = sc->lights[i];
+  return WPT_OK;
+}
+
+int wpt_debug_scene_presolve(void* h, size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out) {
+  const HostScene* sc = (const HostScene*)h;
+  if (!sc || (n && (!rays || !resolved || !t_out || !id_out))) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  // the host restatement: the same presolve_ray over the scene's planes as
+  // upload_scene lays them out (normal, normal . location)
+  HostPlanes hp{};
+  hp.num_inf = 0;
+  PresolveBoxes pre{};
+  if (sc->use_bvh && sc->shapes.size() > sc->num_inf && sc->num_inf <= 16) {
+    pre = sc->pre;
+    hp.num_inf = sc->num_inf;
+    for (uint32_t i = 0; i < sc->num_inf; i++) {
+      const float* g = sc->shapes[i].g;
+      const V3 loc = mk(g[0], g[1], g[2]), nrm = mk(g[3], g[4], g[5]);
+      hp.planes[i] = HostPlanes::P4{nrm.x, nrm.y, nrm.z, dot(nrm, loc)};
+    }
+  }
+  for (size_t i = 0; i < n; i++) {
+    const float* r = rays + 6 * i;
+    resolved[i] = presolve_ray(hp, pre, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), t_out[i], id_out[i]) ? 1 : 0;
+  }
+  return WPT_OK;
+}
+
+int wpt_debug_scene_guards(void* h, uint32_t* num_guards, float* boxes, uint32_t* leaf_guard) {
+  const HostScene* sc = (const HostScene*)h;
+  if (!sc || !num_guards) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  *num_guards = sc->pre.num_guards;
+  if (boxes) {
+    memcpy(boxes, sc->pre.root, 6 * sizeof(float));
+    memcpy(boxes + 6, sc->pre.guard, 6 * kMaxGuards * sizeof(float));
+  }
+  if (leaf_guard)
+    for (size_t i = 0; i < sc->nodes.size(); i++) leaf_guard[i] = i < sc->leaf_guard.size() ? sc->leaf_guard[i] : ~0u;
   return WPT_OK;
 }
 

@@ -51,6 +51,12 @@ struct DevScene {
   // wave timeline probe (WPT_OPT_PROBE) of this launch, or null: per wave of
   // the grid {start, feed ran dry, end (steady clock ticks), rays taken}
   uint4* probe;
+  // presolve (wpt_presolve.h): root and guard boxes; num_guards 0 = resolves
+  // nothing. In device memory, not in the argument block: k_shade then loads
+  // them where it uses them, not ahead of its loop (30 SGPRs held across
+  // shade_path spilled into VGPRs: 75-77 instead of 72). The last member:
+  // the kernels that do not read it keep their argument offsets.
+  const PresolveBoxes* pre;
 };
 
 struct Stats {
@@ -92,6 +98,7 @@ struct Stats {
   uint64_t stock_deficit = 0, stock_waits = 0, plan_us = 0, stock_us = 0;
   uint64_t stock_rays = 0;  // rays traced into the stock (they count in rays / shadow_rays when consumed)
   uint64_t stock_rays_used = 0;  // of rays + shadow_rays: those of samples taken from the stock
+  uint64_t presolved_rays = 0;   // of rays: resolved by their producer (wpt_presolve.h), never fed to k_extend / k_trace
 };
 
 // Kernel-time accumulators (ms), filled when profiling is on.
@@ -124,12 +131,18 @@ struct KernelTimes {
 // counts (u32): [0] = bounce 0's ray count (k_generate), then per bounce b a
 // 64-bit append counter at u32 index 2 + 2b: low word = rays of bounce b + 1,
 // high word = shadow rays emitted at bounce b (k_shade adds both at once).
+// Those are the rays the traversal kernels see (the front of a stream). The
+// presolved rays of bounce b (wpt_presolve.h; the back of its stream, from the
+// slice's last entry downward, with their hit records already written) are
+// counted in the 64-bit slot at u32 index kResWord + 2b (low word).
 constexpr int kMaxLanes = 8;  // streams made per session (lanes used: nlanes_)
 constexpr uint64_t kMinLanePaths = 1024;  // smaller batches run on one lane
 // after the per-bounce words: rays and shadow rays traced by k_finish (the
 // path-at-a-time tail of RR-only batches)
 constexpr size_t kFinishWord = 2 + 2 * (size_t)kMaxBounces;
-constexpr size_t kCountWords = kFinishWord + 4;  // k_finish: rays, shadow rays, paths, longest path (bounces)
+constexpr size_t kResWord = kFinishWord + 4;     // k_finish: rays, shadow rays, paths, longest path (bounces)
+constexpr size_t kCountWords = kResWord + 2 * ((size_t)kMaxBounces + 1);
+static_assert(kResWord % 2 == 0, "the presolved counts are 64-bit slots");
 constexpr uint32_t kWorkWords = 16;   // device work counters (COUNT builds), see d_work_
 constexpr uint32_t kWorkCopies = 64;  // copies of them, one per blockIdx % 64 (spreads the atomics)
 struct PathSet {
@@ -142,8 +155,12 @@ struct PathSet {
   float4* ro[2] = {nullptr, nullptr};
   float4* rd[2] = {nullptr, nullptr};
   float4* thr[2] = {nullptr, nullptr};
+  // hit records of the two streams (bounce b's at [b & 1]: k_shade(b) reads
+  // them while it writes the presolved rays' records of bounce b + 1)
   float* t = nullptr;
   int32_t* id = nullptr;
+  float* t1 = nullptr;
+  int32_t* id1 = nullptr;
   float4 *so = nullptr, *sd = nullptr, *sc = nullptr;
   uint32_t* counts = nullptr;    // kCountWords, see above
   uint32_t* h_counts = nullptr;  // pinned mirror
@@ -182,6 +199,7 @@ struct Batch {
   int lane0 = 0, nl = 1;
   uint64_t off[kMaxLanes + 1] = {};
   bool fused = false, pnee = false;
+  bool presolve = false;  // its producers resolve plane-or-miss rays (depth-capped batches on BVH scenes)
   int maxb = 0, b = 0;  // bounce cap, next bounce to issue
   bool finished = false;  // the tail ran as k_finish
   State state = kNew;
@@ -239,6 +257,8 @@ class Renderer {
   uint32_t tile() const { return tile_; }
   bool unpack_ranks(const float4* gathered, uint64_t slot, std::string& err);
   bool trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err);
+  // test hook: presolve_ray on the device over caller-given rays
+  bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
   bool shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occ, std::string& err);
   // the recorded wave timelines (WPT_OPT_PROBE), then recording restarts
   bool probe_read(std::vector<uint32_t>& meta, std::vector<uint4>& rec, double& ticks_per_us, std::string& err);
@@ -422,6 +442,7 @@ class Renderer {
   bool refill_issue(Refill& F, int h, uint64_t wt, std::string& err);
   bool stock_prefill(int h, uint64_t budget, std::string& err);  // at a compute call's start
   bool stock_prefill_ = true;  // WPT_OPT_STOCK_PREFILL
+  bool pend_presolve_ = false;           // ... presolved (its presolved counts were cleared and copied)
   bool pend_stock_ = false;              // the last main batch traced stock samples (its rays count when consumed)
   std::deque<Batch*> aq_[2];  // per queue: async batches not yet fully issued, in order
   // A random half's whole rounds traced beside the adaptive half's rounds
@@ -492,8 +513,8 @@ class Renderer {
   uint32_t grid_sh_[2 * kTravVariants] = {};
   uint32_t grid_tr_[4] = {};
   uint32_t grid_shade_ = 512;      // k_shade blocks (kShadeBlock lanes each) resident on the chip (the least occupied variant)
-  uint32_t shade_occ_[16] = {};  // per k_shade variant (x ray counting): resident blocks per CU (0: not yet queried)
-  size_t shade_occ_smem_[16] = {};  // ... for this dynamic LDS size
+  uint32_t shade_occ_[32] = {};  // per k_shade variant (x ray counting): resident blocks per CU (0: not yet queried)
+  size_t shade_occ_smem_[32] = {};  // ... for this dynamic LDS size
   bool fused_ = false;             // WPT_OPT_FUSED: bounce b's extension + bounce b-1's shadow rays in one k_trace for every batch
   // batches below this many paths (adaptive sample rounds) always run fused:
   // one launch per bounce drains one pool of rays instead of two (WPT_OPT_FUSED_BELOW)
@@ -513,6 +534,12 @@ class Renderer {
   uint32_t refill_ = 12, refill_sh_ = 16;  // WPT_OPT_REFILL(_SH): idle lanes before a wave refills
   uint64_t finish_below_ = 1u << 18;  // WPT_OPT_FINISH_BELOW: RR-only batches hand their last paths to k_finish (0: never)
   int finish_every_ = 4;           // WPT_OPT_FINISH_EVERY: bounces between the RR-only batches' live-count reads
+  uint32_t num_guards_ = 0;        // the uploaded scene's guard boxes (0: its rays are never presolved)
+  bool presolve_ = true;           // WPT_OPT_PRESOLVE: producers resolve plane-or-miss extension rays (wpt_presolve.h)
+  // the presolved count of the stream the next traversal launch belongs to
+  // (probing: added to the launch's record, see k_probe_add), or null
+  const uint32_t* probe_res_ = nullptr;
+  int hit_sel_ = 0;                // the hit-record buffers the next traversal launch writes (bounce & 1)
   int batch_lanes_ = 1;            // lanes of the batch being launched (1: full-capacity traversal grids)
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
@@ -566,6 +593,10 @@ class Renderer {
   float4* p_thr_[2] = {nullptr, nullptr};
   float* p_t_ = nullptr;
   int32_t* p_id_ = nullptr;
+  float* p_t1_ = nullptr;
+  int32_t* p_id1_ = nullptr;
+  float* hit_t(int k) const { return k ? p_t1_ : p_t_; }
+  int32_t* hit_id(int k) const { return k ? p_id1_ : p_id_; }
   float4* s_o_ = nullptr;
   float4* s_d_ = nullptr;
   float4* s_c_ = nullptr;
@@ -578,6 +609,9 @@ class Renderer {
   uint32_t* ext_count(int b) const { return b == 0 ? d_counts_ : d_counts_ + 2 + 2 * (b - 1); }
   uint32_t* sh_count(int b) const { return d_counts_ + 3 + 2 * b; }
   unsigned long long* append_ctr(int b) const { return reinterpret_cast<unsigned long long*>(d_counts_ + 2 + 2 * b); }
+  // presolved rays of bounce b's stream (k_shade finds them from append_ctr:
+  // res_ctr(b + 1) = append_ctr(b) + kResWord / 2)
+  unsigned long long* res_ctr(int b) const { return reinterpret_cast<unsigned long long*>(d_counts_ + kResWord + 2 * b); }
 
   bool counting_ = false;
   bool profiling_ = false;

@@ -866,12 +866,51 @@ struct GenParams {
   uint32_t left_type, right_type;
 };
 
-// tracer.rs:175-193. Writes the batch's bounce-0 ray stream (path i at i).
+// Path k of a batch (tracer.rs:175-193): its pixel, sample, rng state after
+// the two jitter draws, camera ray direction and render type.
 // Path k of the progressive order: pixel k mod P, sample k div P; or, with
 // rnd_off (a sample round, wpt_adaptive.h, or a stock batch, wpt_stock.h),
 // the entry p whose consecutive range [rnd_off[p], rnd_off[p+1]) holds k,
 // sample rnd_base[p] + k - rnd_off[p]; entry p is pixel rnd_list[p] when
 // given (a stock refill over a half's pixel list), else partition pixel p.
+struct GenPath {
+  uint32_t pl, sample, pixel, s, type;
+  V3 v;
+};
+__device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* __restrict__ part_pix, uint64_t k,
+                                            const uint32_t* __restrict__ rnd_off,
+                                            const uint32_t* __restrict__ rnd_base,
+                                            const uint32_t* __restrict__ rnd_list) {
+  GenPath g;
+  if (rnd_off) {
+    uint32_t lo = 0, hi = P.npix;  // largest p with rnd_off[p] <= k
+    while (lo + 1u < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if ((uint64_t)rnd_off[mid] <= k) lo = mid;
+      else hi = mid;
+    }
+    g.pl = lo;
+    g.sample = rnd_base[lo] + (uint32_t)(k - rnd_off[lo]);
+  } else {
+    g.pl = (uint32_t)(k % P.npix);
+    g.sample = (uint32_t)(k / P.npix);
+  }
+  g.pixel = rnd_list ? rnd_list[g.pl] : part_pix ? part_pix[g.pl] : g.pl;
+  const uint32_t x = g.pixel % P.W, y = g.pixel / P.W;
+  uint32_t s = path_seed(P.seed, g.pixel, g.sample);
+  const float fx = (((float)x + xs_next(s)) * P.w_inv - 0.5f) * P.ar;
+  const float fy = 0.5f - ((float)y + xs_next(s)) * P.h_inv;
+  V3 v = normalize(mk(fx, fy, 0.8f));
+  v = mk(v.x, P.cx * v.y - P.sx * v.z, P.sx * v.y + P.cx * v.z);        // rot_x (vec3.rs:108-119)
+  v = mk(P.cy * v.x + P.sy * v.z, v.y, (-P.sy) * v.x + P.cy * v.z);     // rot_y (vec3.rs:95-106)
+  g.s = s;
+  g.v = v;
+  g.type = x < P.half ? P.left_type : P.right_type;
+  return g;
+}
+
+// Writes the batch's bounce-0 ray stream (path i at i): the kernel of batches
+// that presolve nothing (RR-only, no BVH, WPT_OPT_PRESOLVE = 0).
 // A stock batch (stock_slots != 0) writes the path's stock slot, pixel x
 // slots + sample mod slots, instead of its pixel.
 __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t* __restrict__ part_pix, uint64_t k0,
@@ -885,35 +924,81 @@ __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i == 0) *count0 = n;
   if (i >= n) return;
-  const uint64_t k = k0 + i;
-  uint32_t pl, sample;
-  if (rnd_off) {
-    uint32_t lo = 0, hi = P.npix;  // largest p with rnd_off[p] <= k
-    while (lo + 1u < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if ((uint64_t)rnd_off[mid] <= k) lo = mid;
-      else hi = mid;
-    }
-    pl = lo;
-    sample = rnd_base[lo] + (uint32_t)(k - rnd_off[lo]);
-  } else {
-    pl = (uint32_t)(k % P.npix);
-    sample = (uint32_t)(k / P.npix);
-  }
-  const uint32_t pixel = rnd_list ? rnd_list[pl] : part_pix ? part_pix[pl] : pl;
-  const uint32_t x = pixel % P.W, y = pixel / P.W;
-  uint32_t s = path_seed(P.seed, pixel, sample);
-  const float fx = (((float)x + xs_next(s)) * P.w_inv - 0.5f) * P.ar;
-  const float fy = 0.5f - ((float)y + xs_next(s)) * P.h_inv;
-  V3 v = normalize(mk(fx, fy, 0.8f));
-  v = mk(v.x, P.cx * v.y - P.sx * v.z, P.sx * v.y + P.cx * v.z);        // rot_x (vec3.rs:108-119)
-  v = mk(P.cy * v.x + P.sy * v.z, v.y, (-P.sy) * v.x + P.cy * v.z);     // rot_y (vec3.rs:95-106)
-  const uint32_t type = x < P.half ? P.left_type : P.right_type;
-  pix_out[i] = stock_slots ? pixel * stock_slots + (sample & (stock_slots - 1u)) : rnd_off ? pl : pixel;
-  thr[i] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(type << kTypeShift));
+  const GenPath g = gen_path(P, part_pix, k0 + i, rnd_off, rnd_base, rnd_list);
+  pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+  thr[i] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(g.type << kTypeShift));
   col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  ro[i] = make_float4(P.cam[0], P.cam[1], P.cam[2], __uint_as_float(s));  // w: the path's rng state
-  rd[i] = make_float4(v.x, v.y, v.z, __uint_as_float(i));                // w: the path's index in the batch
+  ro[i] = make_float4(P.cam[0], P.cam[1], P.cam[2], __uint_as_float(g.s));  // w: the path's rng state
+  rd[i] = make_float4(g.v.x, g.v.y, g.v.z, __uint_as_float(i));            // w: the path's index in the batch
+}
+
+// The same for a presolving batch: the stream is two-ended (wpt_presolve.h).
+// A block scans its paths' verdicts and reserves both ranges with one atomic
+// instruction (two lanes, two addresses); unresolved rays go to the front
+// (count0), resolved ones to the back, from entry n - 1 downward, with their
+// hit record (t, id) beside them (res0 counts them). The radiance, pixel and
+// rng state of a path stay at its batch index, so the frame does not depend
+// on where its ray lands.
+__global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint32_t* __restrict__ part_pix, uint64_t k0,
+                                                        uint32_t n, uint32_t* __restrict__ pix_out,
+                                                        float4* __restrict__ thr,
+                                                        float4* __restrict__ col, float4* __restrict__ ro,
+                                                        float4* __restrict__ rd, uint32_t* __restrict__ count0,
+                                                        const uint32_t* __restrict__ rnd_off,
+                                                        const uint32_t* __restrict__ rnd_base,
+                                                        const uint32_t* __restrict__ rnd_list, uint32_t stock_slots,
+                                                        DevScene S, float* __restrict__ t_out,
+                                                        int32_t* __restrict__ id_out, uint32_t* __restrict__ res0) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  constexpr uint32_t kWaves = kBlock / 64;
+  __shared__ uint32_t s_off[2][kWaves];
+  const bool valid = i < n;  // every thread of the block takes part in the scan
+  const GenPath g = gen_path(P, part_pix, k0 + (valid ? i : 0u), rnd_off, rnd_base, rnd_list);
+  float pt;
+  int32_t pid;
+  const bool res = valid && presolve_ray(S, *S.pre, mk(P.cam[0], P.cam[1], P.cam[2]), g.v, pt, pid);
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const uint64_t hm = __ballot(valid && !res), rm = __ballot(res);
+  if (lane == 0) {
+    s_off[0][wid] = (uint32_t)__popcll(hm);
+    s_off[1][wid] = (uint32_t)__popcll(rm);
+  }
+  __syncthreads();
+  if (wid == 0) {
+    const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
+    uint32_t ia = a, ib = b;
+#pragma unroll
+    for (uint32_t q = 1; q < kWaves; q <<= 1) {
+      const uint32_t ya = __shfl_up(ia, q, 64), yb = __shfl_up(ib, q, 64);
+      if (lane >= q) { ia += ya; ib += yb; }
+    }
+    // lane kWaves - 1 holds both totals; lane kWaves adds the second one
+    const uint32_t tb = (uint32_t)__shfl((int)ib, (int)(kWaves - 1), 64);
+    uint32_t base = 0u;
+    if (lane == kWaves - 1 || lane == kWaves) base = atomicAdd(lane == kWaves - 1 ? count0 : res0, lane == kWaves - 1 ? ia : tb);
+    const uint32_t ba = (uint32_t)__shfl((int)base, (int)(kWaves - 1), 64);
+    const uint32_t bb = (uint32_t)__shfl((int)base, (int)kWaves, 64);
+    if (lane < kWaves) {
+      s_off[0][lane] = ba + ia - a;
+      s_off[1][lane] = bb + ib - b;
+    }
+  }
+  __syncthreads();
+  if (!valid) return;
+  uint32_t p;  // the ray's entry in the stream
+  if (res) {
+    p = n - 1u - (s_off[1][wid] + (uint32_t)__popcll(rm & below));
+    t_out[p] = pt;
+    id_out[p] = pid;
+  } else {
+    p = s_off[0][wid] + (uint32_t)__popcll(hm & below);
+  }
+  pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+  col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(g.type << kTypeShift));
+  ro[p] = make_float4(P.cam[0], P.cam[1], P.cam[2], __uint_as_float(g.s));  // w: the path's rng state
+  rd[p] = make_float4(g.v.x, g.v.y, g.v.z, __uint_as_float(i));            // w: the path's index in the batch
 }
 
 template <bool TRI_ONLY>
@@ -1323,18 +1408,38 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
 // word) reserves both output ranges. Blocks append in completion order; a
 // path's result does not depend on its position, so the frame is the same
 // bits for any order (col and the accumulation are indexed by path).
+// PS (presolve, a template parameter: batches that presolve nothing, that is
+// RR-only batches, scenes without a BVH and WPT_OPT_PRESOLVE = 0, run the
+// two-count kernel above unchanged, at its own register count; the two-ended
+// bookkeeping measured -1.2 % on C2 when every batch paid it).
+// With PS the streams are two-ended (wpt_presolve.h): entries 0..nh-1
+// (count) are the rays the traversal kernel traced, the nr entries from end-1
+// downward (res_in) the rays their producer resolved, hit records beside both.
+// A survivor's next ray is presolved here; resolved ones are appended to the
+// back of the next stream with their record (t_nx, id_nx: the other pair of
+// hit-record buffers, since this launch still reads t_in / id_in). The third
+// count is reserved in the same scan; its atomic is the same instruction as
+// the append counter's: lanes kWaves-1 and kWaves, two addresses.
 // OCT (PNEE): where photon_sample reads the octree: 0 global memory, 1 the
 // child array from LDS, 2 child array and CDFs from LDS (oct_lds_words).
-template <bool TRI_ONLY, bool PNEE, int OCT, bool CR = false>
+template <bool TRI_ONLY, bool PNEE, int OCT, bool CR = false, bool PS = false>
 __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in, RayStream out,
                                                        ShadowStream sh, float4* __restrict__ col,
                                                        const uint32_t* __restrict__ count, const float* __restrict__ t_in,
                                                        const int32_t* __restrict__ id_in,
-                                                       unsigned long long* __restrict__ append) {
+                                                       unsigned long long* __restrict__ append,
+                                                       float* __restrict__ t_nx, int32_t* __restrict__ id_nx,
+                                                       uint32_t end) {
   constexpr uint32_t kWaves = kShadeBlock / 64;
-  __shared__ uint32_t s_off[2][kWaves];
+  static_assert(kWaves < 64, "the scan's totals and the second atomic lane sit in one wave");
+  __shared__ uint32_t s_off[PS ? 3 : 2][kWaves];
   __shared__ f4v s_light[5 * kShadeLights];
-  const uint32_t n = *count;
+  const uint32_t nh = *count;
+  // the presolved counts sit at fixed distances from the append counter
+  // (kResWord, wpt_render.h): this bounce's 2 words before the slot of the
+  // next bounce's, which is kResWord words past `append` (no further
+  // arguments: the NEE variant's scalar registers are all in use)
+  const uint32_t n = PS ? nh + reinterpret_cast<const uint32_t*>(append)[kResWord - 2] : nh;
   // the light records (5 float4 each) into LDS when they fit: the NEE light
   // pick is then an LDS read instead of a dependent global round trip
   const bool lds_lights = S.num_lights <= kShadeLights;
@@ -1372,38 +1477,85 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
     const uint32_t i = i0 + threadIdx.x;
     ShadeOut R;
     R.alive = R.shadow = false;
-    if (i < n)
-      shade_path<TRI_ONLY, PNEE, OV, CR>(S, O, P, col, t_in[i], id_in[i], in.o[i], in.d[i], in.thr[i], R,
+    if (i < n) {
+      const uint32_t q = !PS || i < nh ? i : end - 1u - (i - nh);  // front, then the back downward
+      shade_path<TRI_ONLY, PNEE, OV, CR>(S, O, P, col, t_in[q], id_in[q], in.o[q], in.d[q], in.thr[q], R,
                                      lds_lights ? (const lds_f4v*)s_light : nullptr);
-    const uint64_t am = __ballot(R.alive), sm = __ballot(R.shadow);
+    }
+    bool res = false;
+    float pt = 0.0f;
+    int32_t pid = -1;
+    if constexpr (PS) {
+      if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
+    }
+    const uint64_t am = __ballot(R.alive && !res), sm = __ballot(R.shadow), rm = PS ? __ballot(res) : 0ull;
     if (lane == 0) {
       s_off[0][wid] = (uint32_t)__popcll(am);
       s_off[1][wid] = (uint32_t)__popcll(sm);
+      if constexpr (PS) s_off[2][wid] = (uint32_t)__popcll(rm);
     }
     __syncthreads();
-    if (wid == 0) {
+    if constexpr (!PS) {
+      if (wid == 0) {
+        const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
+        uint32_t ia = a, ib = b;
+#pragma unroll
+        for (uint32_t k = 1; k < kWaves; k <<= 1) {
+          const uint32_t ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64);
+          if (lane >= k) { ia += ya; ib += yb; }
+        }
+        unsigned long long base = 0ull;
+        if (lane == kWaves - 1) base = atomicAdd(append, (unsigned long long)ia | ((unsigned long long)ib << 32));
+        const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
+        const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
+        if (lane < kWaves) {
+          s_off[0][lane] = ba + ia - a;
+          s_off[1][lane] = bb + ib - b;
+        }
+      }
+    } else if (wid == 0) {
       const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
-      uint32_t ia = a, ib = b;
+      const uint32_t c = lane < kWaves ? s_off[2][lane] : 0u;
+      uint32_t ia = a, ib = b, ic = c;
 #pragma unroll
       for (uint32_t k = 1; k < kWaves; k <<= 1) {
-        const uint32_t ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64);
-        if (lane >= k) { ia += ya; ib += yb; }
+        const uint32_t ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64), yc = __shfl_up(ic, k, 64);
+        if (lane >= k) { ia += ya; ib += yb; ic += yc; }
       }
+      const uint32_t tc = (uint32_t)__shfl((int)ic, (int)(kWaves - 1), 64);
       unsigned long long base = 0ull;
-      if (lane == kWaves - 1) base = atomicAdd(append, (unsigned long long)ia | ((unsigned long long)ib << 32));
+      // the second counter's distance, made here: as a plain constant the
+      // compiler keeps it in a VGPR across the whole loop (shade_path's peak)
+      uint32_t off;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)(kResWord / 2)));
+      if (lane == kWaves - 1 || lane == kWaves)
+        base = atomicAdd(append + (lane == kWaves - 1 ? 0u : off),
+                         lane == kWaves - 1 ? ((unsigned long long)ia | ((unsigned long long)ib << 32))
+                                            : (unsigned long long)tc);
       const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
       const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
+      const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
       if (lane < kWaves) {
         s_off[0][lane] = ba + ia - a;
         s_off[1][lane] = bb + ib - b;
+        s_off[2][lane] = bc + ic - c;
       }
     }
     __syncthreads();
     if (R.alive) {
-      const uint32_t p = s_off[0][wid] + (uint32_t)__popcll(am & below);
+      uint32_t p = s_off[0][wid] + (uint32_t)__popcll(am & below);
+      if constexpr (PS) {
+        if (res) p = end - 1u - (s_off[2][wid] + (uint32_t)__popcll(rm & below));
+      }
       st_stream(out.o + p, R.ro);
       st_stream(out.d + p, R.rd);
       st_stream(out.thr + p, R.th);
+      if constexpr (PS) {
+        if (res) {
+          t_nx[p] = pt;
+          id_nx[p] = pid;
+        }
+      }
     }
     if (R.shadow) {
       const uint32_t p = s_off[1][wid] + (uint32_t)__popcll(sm & below);
@@ -1947,6 +2099,29 @@ __global__ void __launch_bounds__(kTBlock, TRI_ONLY ? WPT_FINISH_WAVES : 1) k_fi
   }
 }
 
+// Probing a launch whose stream is two-ended: the rays their producer
+// resolved never reach a wave, so they are added to the first wave's "rays
+// taken" of the bounce's traversal launch; a launch's entries then still sum
+// to the bounce's rays, as the statistics count them. Launched only while
+// the probe records.
+__global__ void k_probe_add(uint4* rec, const uint32_t* __restrict__ res) { rec[0].w += *res; }
+
+// Test hook: presolve_ray (wpt_presolve.h) as the producers run it, over
+// caller-given rays (6 floats each: origin, direction).
+__global__ void __launch_bounds__(kBlock) k_presolve(DevScene S, uint32_t n, const float* __restrict__ rays,
+                                                     uint8_t* __restrict__ resolved, float* __restrict__ t_out,
+                                                     int32_t* __restrict__ id_out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  float t;
+  int32_t id;
+  const bool res = presolve_ray(S, *S.pre, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), t, id);
+  resolved[i] = res ? 1 : 0;
+  t_out[i] = t;
+  id_out[i] = id;
+}
+
 // RenderTarget::write (render_target.rs:55-58): acc += v, count += 1, per
 // pixel in increasing sample order (slots j, j+npix, ... are one pixel).
 __global__ void __launch_bounds__(kBlock) k_accumulate(const uint32_t* __restrict__ part_pix, uint64_t k0, uint32_t n,
@@ -2190,14 +2365,15 @@ void Renderer::free_scene() {
 }
 
 void Renderer::free_lane_paths(PathSet& L) {
-  void* bufs[] = {L.pixel, L.col, L.ro[0], L.rd[0], L.thr[0], L.ro[1], L.rd[1], L.thr[1], L.t, L.id, L.so, L.sd, L.sc};
+  void* bufs[] = {L.pixel, L.col, L.ro[0], L.rd[0], L.thr[0], L.ro[1], L.rd[1], L.thr[1], L.t, L.id, L.t1, L.id1,
+                  L.so, L.sd, L.sc};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   L.pixel = nullptr;
   L.col = nullptr;
   for (int k = 0; k < 2; k++) L.ro[k] = L.rd[k] = L.thr[k] = nullptr;
-  L.t = nullptr;
-  L.id = nullptr;
+  L.t = L.t1 = nullptr;
+  L.id = L.id1 = nullptr;
   L.so = L.sd = L.sc = nullptr;
   L.cap = 0;
 }
@@ -2221,6 +2397,7 @@ void Renderer::bind_lane(int i) {
     p_thr_[k] = L.thr[k];
   }
   p_t_ = L.t; p_id_ = L.id;
+  p_t1_ = L.t1; p_id1_ = L.id1;
   s_o_ = L.so; s_d_ = L.sd; s_c_ = L.sc;
   d_counts_ = L.counts; h_counts_ = L.h_counts;
   d_spill_ = L.spill; spill_cap_ = L.spill_cap;
@@ -2400,6 +2577,13 @@ bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
   ds.refill_lanes_sh = refill_sh_;
   for (int k = 0; k < 3; k++) ds.bg[k] = sc.background[k];
   for (uint32_t i = 0; i < sc.num_inf && i < (uint32_t)kMaxInf; i++) ds.planes[i] = all[4 * i];
+  {
+    PresolveBoxes pre{};  // num_guards = 0: nothing resolves
+    if (sc.use_bvh && nf != 0) pre = sc.pre;
+    if (!up(&pre, sizeof pre, &p)) return false;
+    ds.pre = (const PresolveBoxes*)p;
+    num_guards_ = pre.num_guards;
+  }
   ds_ = ds;
   depth_ = sc.depth;
   ds_.stack_cap = (int)std::max<uint32_t>(sc.depth + 2, 3 * sc.depth4 + 4);
@@ -2462,6 +2646,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 34: if (!range(0, 1)) return false; log_ = (int)v; return true;
     case 35: if (!range(0, 1)) return false; stock_prefill_ = v != 0; return true;
     case 36: if (!range(0, (int64_t)1 << 40)) return false; async_fused_below_ = (uint64_t)v; return true;
+    case 37: if (!range(0, 1)) return false; presolve_ = v != 0; return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -2513,6 +2698,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 34: v = log_; return true;
     case 35: v = stock_prefill_ ? 1 : 0; return true;
     case 36: v = (int64_t)async_fused_below_; return true;
+    case 37: v = presolve_ ? 1 : 0; return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -2764,13 +2950,17 @@ int Renderer::main_lanes() const {
 // One lane's count words of a finished batch into st: the rays of bounces
 // 0 .. b-1 (bounce 0: k_generate's count, bounce i: the append counter of
 // bounce i-1), the shadow rays of each bounce, k_finish's rays and paths.
-static void add_counts(Stats& st, const uint32_t* hc, int b, bool stock) {
+static void add_counts(Stats& st, const uint32_t* hc, int b, bool stock, bool presolve) {
   // a stock batch's rays count when a round takes its samples (k_consume)
   uint64_t& r = stock ? st.stock_rays : st.rays;
   uint64_t& sr = stock ? st.stock_rays : st.shadow_rays;
   for (int i = 0; i < b; i++) {
-    r += i == 0 ? hc[0] : hc[2 + 2 * (i - 1)];
+    // the rays k_extend / k_trace saw plus those their producer resolved
+    // (a batch that presolves nothing neither clears nor copies those words)
+    const uint32_t res = presolve ? hc[kResWord + 2 * i] : 0u;
+    r += (i == 0 ? hc[0] : hc[2 + 2 * (i - 1)]) + res;
     sr += hc[3 + 2 * i];
+    st.presolved_rays += res;  // (a stock batch's too, when traced)
   }
   r += hc[kFinishWord];
   sr += hc[kFinishWord + 1];
@@ -2784,14 +2974,14 @@ bool Renderer::flush_counts(std::string& err) {
   if (!stats_pending_) return true;
   for (int l = 0; l < pend_nl_; l++)
     if (!host_wait(lanes_[l].done, err)) return false;
-  for (int l = 0; l < pend_nl_; l++) add_counts(stats_, lanes_[l].h_counts, pend_b_, pend_stock_);
+  for (int l = 0; l < pend_nl_; l++) add_counts(stats_, lanes_[l].h_counts, pend_b_, pend_stock_, pend_presolve_);
   stats_pending_ = false;
   return true;
 }
 
 // A finished async batch's counts (its done events waited for by the caller).
 void Renderer::batch_counts(const Batch& B, const uint32_t* hc) {
-  for (int i = 0; i < B.nl; i++) add_counts(stats_, hc + (size_t)i * kCountWords, B.b, B.stock);
+  for (int i = 0; i < B.nl; i++) add_counts(stats_, hc + (size_t)i * kCountWords, B.b, B.stock, B.presolve);
   stats_.bounces += (uint64_t)B.b;
 }
 
@@ -2819,22 +3009,38 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   G.left_type = (uint32_t)left_type_; G.right_type = (uint32_t)right_type_;
   const uint32_t slots = B.stock ? stock_used_slots_ : 0u;
   for (int i = 0; i <= B.nl; i++) B.off[i] = B.n * (uint64_t)i / (uint64_t)B.nl;
+  // RR-only batches (the k_finish hand-over reads one live count per lane)
+  // run without the presolve
+  B.presolve = presolve_ && max_depth_ > 0 && num_guards_ != 0;
   if (time_launches_) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
   batch_lanes_ = B.nl;
   for (int i = 0; i < B.nl; i++) {
     const int l = B.lane0 + i;
+    if (B.presolve && !lanes_[l].t1 && lanes_[l].cap) {
+      // the second pair of hit records, made with the lane's first presolving
+      // batch: sessions that presolve nothing allocate what they did before
+      HIP_OK(hipMalloc(&lanes_[l].t1, 4 * lanes_[l].cap));
+      HIP_OK(hipMalloc(&lanes_[l].id1, 4 * lanes_[l].cap));
+    }
     bind_batch_lane(B, l);
     if (B.off[i + 1] - B.off[i] > cap_) { bind_lane(0); err = "batch exceeds lane capacity"; return false; }
     if (l != 0) HIP_OK(hipStreamWaitEvent(ks_, ev_main_, 0));  // after reset / round planning on the main stream
     // a low-priority stream after the lane's last main batch (its buffers)
     if (ks_ != lanes_[l].stream) HIP_OK(hipStreamWaitEvent(ks_, lanes_[l].done, 0));
     const uint32_t nn = (uint32_t)(B.off[i + 1] - B.off[i]);
-    HIP_OK(hipMemsetAsync(d_counts_, 0, sizeof(uint32_t) * kCountWords, ks_));
-    LAUNCH_TIMED(0, generate, n_generate,
-                 k_generate<<<blocks_for(nn), kBlock, 0, ks_>>>(G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0],
-                                                              p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off, rnd_base,
-                                                              B.mlist, slots));
+    // (the presolved counts, the words from kResWord on, only where they are used)
+    HIP_OK(hipMemsetAsync(d_counts_, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), ks_));
+    if (B.presolve)
+      LAUNCH_TIMED(0, generate, n_generate,
+                   k_generate_ps<<<blocks_for(nn), kBlock, 0, ks_>>>(
+                       G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0], p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off,
+                       rnd_base, B.mlist, slots, ds_, p_t_, p_id_, reinterpret_cast<uint32_t*>(res_ctr(0))));
+    else
+      LAUNCH_TIMED(0, generate, n_generate,
+                   k_generate<<<blocks_for(nn), kBlock, 0, ks_>>>(G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0],
+                                                                p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off, rnd_base,
+                                                                B.mlist, slots));
   }
   B.maxb = max_depth_ > 0 ? std::min(max_depth_, kMaxBounces) : kMaxBounces;
   // fused: bounce b >= 1 traces its extension rays together with bounce b-1's
@@ -2932,12 +3138,15 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
     for (int i = 0; i < B.nl; i++) {
       bind_batch_lane(B, B.lane0 + i);
       const uint32_t nn = (uint32_t)(B.off[i + 1] - B.off[i]);
-      if (B.fused && b > 0) {
-        if (!launch_trace(b, err)) { bind_lane(0); return false; }
-      } else if (!launch_extend(p_ro_[b & 1], p_rd_[b & 1], ext_count(b), err)) {
-        bind_lane(0);
-        return false;
-      }
+      // (batches that presolve nothing keep one pair of hit-record buffers, as before)
+      const int hs = B.presolve ? (b & 1) : 0;
+      hit_sel_ = hs;
+      probe_res_ = B.presolve ? reinterpret_cast<const uint32_t*>(res_ctr(b)) : nullptr;
+      const bool traced = (B.fused && b > 0) ? launch_trace(b, err)
+                                             : launch_extend(p_ro_[b & 1], p_rd_[b & 1], ext_count(b), err);
+      hit_sel_ = 0;
+      probe_res_ = nullptr;
+      if (!traced) { bind_lane(0); return false; }
       {
         const RayStream in{p_ro_[b & 1], p_rd_[b & 1], p_thr_[b & 1]};
         const RayStream out{p_ro_[(b + 1) & 1], p_rd_[(b + 1) & 1], p_thr_[(b + 1) & 1]};
@@ -2947,34 +3156,38 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
         // the persistent grid of the variant launched: its own occupancy
         // (VGPRs, and the octree's LDS for OC), cached per variant and LDS size
 #if WPT_SHADE_GRID_VAR
-#define WPT_SHADE_GRID(T, PN, OC, CR)                                                                           \
-  const int vi = (CR ? 8 : 0) + (T ? 4 : 0) + (PN ? 1 + OC : 0);                                                \
+#define WPT_SHADE_GRID(T, PN, OC, CR, PS)                                                                       \
+  const int vi = (PS ? 16 : 0) + (CR ? 8 : 0) + (T ? 4 : 0) + (PN ? 1 + OC : 0);                                \
   const size_t smem = OC ? 4 * (size_t)ds_.oct_lds_words : 0;                                                   \
   if (shade_occ_[vi] == 0 || shade_occ_smem_[vi] != smem) {                                                     \
     int bpc = 0;                                                                                                \
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_shade<T, PN, OC, CR>, (int)kShadeBlock, smem));  \
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_shade<T, PN, OC, CR, PS>, (int)kShadeBlock, smem)); \
     shade_occ_[vi] = (uint32_t)std::max(bpc, 1);                                                                \
     shade_occ_smem_[vi] = smem;                                                                                 \
   }                                                                                                             \
   const uint32_t sg = std::max<uint32_t>(1, std::min<uint32_t>((nn + kShadeBlock - 1) / kShadeBlock,            \
                                                                (uint32_t)ncu_ * shade_occ_[vi]));
 #else
-#define WPT_SHADE_GRID(T, PN, OC, CR) const uint32_t sg = sgrid;
+#define WPT_SHADE_GRID(T, PN, OC, CR, PS) const uint32_t sg = sgrid;
 #endif
-#define WPT_SHADE1(T, PN, OC, CR)                                                                                   \
+#define WPT_SHADE1(T, PN, OC, CR, PS)                                                                               \
   do {                                                                                                              \
-    WPT_SHADE_GRID(T, PN, OC, CR)                                                                                   \
+    WPT_SHADE_GRID(T, PN, OC, CR, PS)                                                                               \
     const uint32_t sgo = async_launch_ && async_oneshot_ ? std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock) \
                                                          : sg;                                                      \
     LAUNCH_TIMED(2, shade, n_shade,                                                                                 \
-                 k_shade<T, PN, OC, CR><<<sgo, kShadeBlock, OC ? 4 * ds_.oct_lds_words : 0, ks_>>>(                 \
-                     ds_, SP, in, out, sh, p_col_, ext_count(b), p_t_, p_id_, append_ctr(b)));                      \
+                 k_shade<T, PN, OC, CR, PS><<<sgo, kShadeBlock, OC ? 4 * ds_.oct_lds_words : 0, ks_>>>(             \
+                     ds_, SP, in, out, sh, p_col_, ext_count(b), hit_t(hs), hit_id(hs), append_ctr(b),             \
+                     hit_t(hs ^ 1), hit_id(hs ^ 1), nn));                                                           \
   } while (0)
 // a stock batch's paths write their ray counts (CR)
 #define WPT_SHADE(T, PN, OC)              \
   do {                                    \
-    if (B.stock) WPT_SHADE1(T, PN, OC, true); \
-    else WPT_SHADE1(T, PN, OC, false);    \
+    if (B.presolve) {                                \
+      if (B.stock) WPT_SHADE1(T, PN, OC, true, true);    \
+      else WPT_SHADE1(T, PN, OC, false, true);           \
+    } else if (B.stock) WPT_SHADE1(T, PN, OC, true, false); \
+    else WPT_SHADE1(T, PN, OC, false, false);            \
   } while (0)
         // PNEE: the octree from LDS when oct_lds_words covers it (child array and CDFs, or the child array)
         const int oc = !B.pnee || ds_.oct_lds_words == 0 ? 0 : (ds_.oct_lds_words > ds_.oct_nodes ? 2 : 1);
@@ -3049,7 +3262,8 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
     HIP_OK(hipGetLastError());
     // ray statistics from the per-bounce counts (done: after this copy too)
     uint32_t* hc = B.async ? B.hc + (size_t)i * kCountWords : h_counts_;
-    HIP_OK(hipMemcpyAsync(hc, d_counts_, sizeof(uint32_t) * kCountWords, hipMemcpyDeviceToHost, ks_));
+    HIP_OK(hipMemcpyAsync(hc, d_counts_, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord),
+                          hipMemcpyDeviceToHost, ks_));
     HIP_OK(hipEventRecord(B.async ? B.done[i] : lanes_[l].done, ks_));
   }
   bind_lane(0);
@@ -3058,6 +3272,7 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
     pend_nl_ = B.nl;
     pend_b_ = B.b;
     pend_stock_ = B.stock;
+    pend_presolve_ = B.presolve;
     stats_pending_ = true;
   }
   B.state = Batch::kIssued;
@@ -3837,7 +4052,8 @@ bool Renderer::launch_extend(const float4* ro, const float4* rd, const uint32_t*
   const uint32_t g = std::min(async_grid(grid_ext_[v + full], 100), spill_grid());
   ds_.probe = probe_slot(1, g);
 #define WPT_EXT(T, C, F) \
-  k_extend<T, C, F><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, cnt, p_t_, p_id_, d_spill_, d_work_, d_fallback_)
+  k_extend<T, C, F><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, cnt, hit_t(hit_sel_), hit_id(hit_sel_), d_spill_, d_work_, \
+                                            d_fallback_)
   switch (v) {
     case 0: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(false, false, 0)); break;
     case 1: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, false, 0)); break;
@@ -3849,6 +4065,10 @@ bool Renderer::launch_extend(const float4* ro, const float4* rd, const uint32_t*
     default: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, true, 1)); break;
   }
 #undef WPT_EXT
+  if (ds_.probe && probe_res_) {
+    k_probe_add<<<1, 1, 0, ks_>>>(ds_.probe, probe_res_);
+    HIP_OK(hipGetLastError());
+  }
   ds_.probe = nullptr;
   return true;
 }
@@ -3888,7 +4108,8 @@ bool Renderer::launch_trace(int b, std::string& err) {
   const uint32_t* cs = sh_count(b - 1);
   ds_.probe = probe_slot(5, g);
 #define WPT_TR(T, C) \
-  k_trace<T, C><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, ce, p_t_, p_id_, cs, s_o_, s_d_, s_c_, p_col_, d_spill_, d_work_)
+  k_trace<T, C><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, ce, hit_t(hit_sel_), hit_id(hit_sel_), cs, s_o_, s_d_, s_c_, \
+                                        p_col_, d_spill_, d_work_)
   switch (v) {
     case 0: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(false, false)); break;
     case 1: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(true, false)); break;
@@ -3896,6 +4117,10 @@ bool Renderer::launch_trace(int b, std::string& err) {
     default: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(true, true)); break;
   }
 #undef WPT_TR
+  if (ds_.probe && probe_res_) {
+    k_probe_add<<<1, 1, 0, ks_>>>(ds_.probe, probe_res_);
+    if (hipGetLastError() != hipSuccess) { err = "k_probe_add launch failed"; ds_.probe = nullptr; return false; }
+  }
   ds_.probe = nullptr;
   (void)err;
   return true;
@@ -4533,6 +4758,34 @@ bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id
   HIP_OK(hipMemcpyAsync(id_out, p_id_, 4 * n, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   return true;
+}
+
+bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out,
+                             std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (n == 0) return true;
+  if (n > 0xFFFFFFFFull / 8) { err = "too many rays"; return false; }
+  float* dr = nullptr;
+  float* dt = nullptr;
+  int32_t* di = nullptr;
+  uint8_t* df = nullptr;
+  bool ok = hipMalloc(&dr, 24 * n) == hipSuccess && hipMalloc(&dt, 4 * n) == hipSuccess &&
+            hipMalloc(&di, 4 * n) == hipSuccess && hipMalloc(&df, n) == hipSuccess;
+  if (ok) ok = hipMemcpyAsync(dr, rays, 24 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
+  if (ok) {
+    k_presolve<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dr, df, dt, di);
+    ok = hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(t_out, dt, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(id_out, di, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipStreamSynchronize(stream_) == hipSuccess;
+  }
+  (void)hipFree(dr);
+  (void)hipFree(dt);
+  (void)hipFree(di);
+  (void)hipFree(df);
+  if (!ok) err = "HIP error in presolve_rays";
+  return ok;
 }
 
 // Parity hook: the production shadow kernel on caller-given (p, q, light);

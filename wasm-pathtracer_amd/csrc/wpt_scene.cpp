@@ -355,6 +355,85 @@ void build_bvh4(HostScene& sc) {
   c.fill(0, kids);
 }
 
+// Guard boxes of the presolve. Start with one group holding every leaf of the
+// BVH2; repeatedly split the group with the largest box area at the widest
+// empty gap between its leaf boxes' intervals along any axis (a gap: a
+// coordinate range no leaf interval of the group overlaps); stop at
+// kMaxGuards groups or when no group has a gap. A guard is the min/max union
+// of the f32 bounds as stored in the nodes, so every leaf box lies inside its
+// guard bit for bit, which is all the exactness argument (wpt_presolve.h)
+// needs; how the groups are chosen only decides how many rays resolve.
+void build_guards(HostScene& sc) {
+  sc.pre = PresolveBoxes{};
+  sc.leaf_guard.assign(sc.nodes.size(), ~0u);
+  if (sc.shapes.size() <= sc.num_inf || sc.nodes.empty()) return;
+  std::vector<uint32_t> leaves;
+  {
+    std::vector<uint32_t> todo{0u};
+    while (!todo.empty()) {
+      const uint32_t n = todo.back();
+      todo.pop_back();
+      if (sc.nodes[n].count != 0) { leaves.push_back(n); continue; }
+      todo.push_back(sc.nodes[n].left_first);
+      todo.push_back(sc.nodes[n].left_first + 1);
+    }
+  }
+  struct Group {
+    std::vector<uint32_t> leaves;
+    float b[6];
+    bool whole = false;  // no gap on any axis
+  };
+  auto bounds = [&](Group& g) {
+    for (int k = 0; k < 3; k++) { g.b[k] = INFINITY; g.b[3 + k] = -INFINITY; }
+    for (uint32_t n : g.leaves)
+      for (int k = 0; k < 3; k++) {
+        g.b[k] = fminf(g.b[k], sc.nodes[n].bmin[k]);
+        g.b[3 + k] = fmaxf(g.b[3 + k], sc.nodes[n].bmax[k]);
+      }
+  };
+  auto area = [](const Group& g) {
+    const double x = (double)g.b[3] - g.b[0], y = (double)g.b[4] - g.b[1], z = (double)g.b[5] - g.b[2];
+    return x * y + y * z + z * x;
+  };
+  std::vector<Group> groups(1);
+  groups[0].leaves = leaves;
+  bounds(groups[0]);
+  while (groups.size() < (size_t)kMaxGuards) {
+    // the splittable group of the largest area
+    int pick = -1;
+    for (size_t i = 0; i < groups.size(); i++)
+      if (!groups[i].whole && groups[i].leaves.size() > 1 && (pick < 0 || area(groups[i]) > area(groups[pick])))
+        pick = (int)i;
+    if (pick < 0) break;
+    Group& g = groups[pick];
+    float best_gap = 0.0f, cut = 0.0f;
+    int axis = -1;
+    for (int k = 0; k < 3; k++) {
+      std::vector<uint32_t> ord = g.leaves;
+      std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return sc.nodes[a].bmin[k] < sc.nodes[b].bmin[k]; });
+      float hi = sc.nodes[ord[0]].bmax[k];
+      for (size_t i = 1; i < ord.size(); i++) {
+        const float lo = sc.nodes[ord[i]].bmin[k];
+        if (lo > hi && lo - hi > best_gap) { best_gap = lo - hi; cut = lo; axis = k; }
+        hi = fmaxf(hi, sc.nodes[ord[i]].bmax[k]);
+      }
+    }
+    if (axis < 0) { g.whole = true; continue; }
+    Group a, b;
+    for (uint32_t n : g.leaves) (sc.nodes[n].bmin[axis] < cut ? a : b).leaves.push_back(n);
+    bounds(a);
+    bounds(b);
+    groups[pick] = std::move(a);
+    groups.push_back(std::move(b));
+  }
+  sc.pre.num_guards = (uint32_t)groups.size();
+  for (int k = 0; k < 3; k++) { sc.pre.root[k] = sc.nodes[0].bmin[k]; sc.pre.root[3 + k] = sc.nodes[0].bmax[k]; }
+  for (size_t i = 0; i < groups.size(); i++) {
+    for (int k = 0; k < 6; k++) sc.pre.guard[i][k] = groups[i].b[k];
+    for (uint32_t n : groups[i].leaves) sc.leaf_guard[n] = (uint32_t)i;
+  }
+}
+
 bool scene_init(HostScene& sc, std::vector<Shape> shapes, const float bg[3], Bvh2Builder* gpu, std::string* err) {
   sc.background[0] = bg[0]; sc.background[1] = bg[1]; sc.background[2] = bg[2];
   sc.use_bvh = true;
@@ -419,6 +498,7 @@ bool scene_init(HostScene& sc, std::vector<Shape> shapes, const float bg[3], Bvh
   sc.leaf_table.clear();
   sc.depth4 = 0;
   if (sc.want_bvh4 == 1 || (sc.want_bvh4 == 2 && !sc.tri_only && sc.use_bvh)) build_bvh4(sc);
+  build_guards(sc);
   return true;
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "wpt_math.h"
+#include "wpt_presolve.h"
 
 namespace wpt {
 
@@ -63,6 +64,10 @@ struct HostScene {
   int want_bvh4 = 1;  // set before building: collapse the BVH4 (the bvh4 traversal reads it): 0 no, 1 yes, 2 unless triangle-only or without a BVH
   bool bvh_on_gpu = false;           // the BVH2 came from a Bvh2Builder (the GPU build)
   double bvh_ms = 0.0;               // BVH2 build time (host wall clock, or the GPU build's device time)
+  // presolve (wpt_presolve.h): the root box and the guard boxes, and per BVH2
+  // node the guard of a leaf (~0u: not a leaf); filled by build_guards
+  PresolveBoxes pre{};
+  std::vector<uint32_t> leaf_guard;
 };
 
 // A BVH2 builder that replaces the host one (the GPU build, wpt_bvh_gpu.h)
@@ -79,6 +84,11 @@ struct Bvh2Builder {
 
 // Collapse the BVH2 into the fast-path BVH4 (fills nodes4 / leaf_table).
 void build_bvh4(HostScene& sc);
+
+// The presolve's guard boxes (wpt_presolve.h): the BVH2's leaves partitioned
+// into at most kMaxGuards groups, each guard the exact min/max union of its
+// leaves' stored bounds (fills sc.pre and sc.leaf_guard; scene_init calls it).
+void build_guards(HostScene& sc);
 
 // Shape constructors (primitives/*.rs new()).
 Shape make_triangle(V3 a, V3 b, V3 c, bool emissive, V3 m);

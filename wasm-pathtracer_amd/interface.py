@@ -225,7 +225,7 @@ def stats():
             "sum_chunks", "sum_resummed", "sum_fetched", "stock_consumed", "fill_paths", "trace_bytes",
             "finish_paths", "finish_max_bounces", "max_ray_visits", "ex_body_lanes", "ex_bodies", "lf_body_lanes",
             "lf_bodies", "stock_traced", "stock_deficit", "stock_waits", "plan_us", "stock_us",
-            "stock_rays", "stock_rays_used")
+            "stock_rays", "stock_rays_used", "presolved_rays")
     out = (ctypes.c_uint64 * len(keys))()
     _check(lib().wpt_stats(ctypes.addressof(out), len(keys)))
     return dict(zip(keys, list(out)))
@@ -270,7 +270,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "finish_below": 13, "trace_grid_pct": 14, "finish_every": 20, "probe": 22, "stock": 23, "stock_lanes": 24,
            "fill": 25, "async_prio": 26, "async_grid_pct": 27, "scene_traversal": 28, "scene_tri_only": 29,
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
-           "log": 34, "stock_prefill": 35, "async_fused_below": 36}
+           "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -342,6 +342,18 @@ def shadow_rays(pq, light_ids):
     return occ.astype(bool)
 
 
+def presolve_rays(rays):
+    """The producers' presolve on the device (wpt_presolve_rays): per ray
+    (resolved, t, id); (t, id) is the closest hit of a resolved ray."""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    res = np.zeros(n, dtype=np.uint8)
+    t = np.empty(n, dtype=np.float32)
+    ids = np.empty(n, dtype=np.int32)
+    _check(lib().wpt_presolve_rays(n, r.ctypes.data, res.ctypes.data, t.ctypes.data, ids.ctypes.data))
+    return res.astype(bool), t, ids
+
+
 def shutdown():
     _check(lib().wpt_shutdown())
 
@@ -386,6 +398,25 @@ class DebugScene:
         out = np.empty(self.num_lights, dtype=np.uint32)
         lib().wpt_debug_scene_lights(self.h, out.ctypes.data)
         return out
+
+    def presolve(self, rays):
+        """The presolve's host restatement (as presolve_rays, no GPU)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        res = np.zeros(n, dtype=np.uint8)
+        t = np.empty(n, dtype=np.float32)
+        ids = np.empty(n, dtype=np.int32)
+        _check(lib().wpt_debug_scene_presolve(self.h, n, r.ctypes.data, res.ctypes.data, t.ctypes.data,
+                                              ids.ctypes.data))
+        return res.astype(bool), t, ids
+
+    def guards(self):
+        """(root box (6,), guard boxes (n, 6), per-node guard of a leaf or 0xFFFFFFFF)."""
+        ng = ctypes.c_uint32(0)
+        boxes = np.zeros(30, dtype=np.float32)
+        lg = np.zeros(max(self.num_nodes, 1), dtype=np.uint32)
+        _check(lib().wpt_debug_scene_guards(self.h, ctypes.addressof(ng), boxes.ctypes.data, lg.ctypes.data))
+        return boxes[:6].copy(), boxes[6:].reshape(4, 6)[: ng.value].copy(), lg[: self.num_nodes]
 
     def __del__(self):
         try:
