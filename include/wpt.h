@@ -269,7 +269,9 @@ int wpt_seq_sum_device(const float* v, uint64_t n, float* out);
  * shadow; rays and shadow rays count a stocked sample's when a round takes it),
  * out[39] = of rays + shadow rays, those of samples taken from the stock,
  * out[40] = of rays, those their producer resolved (WPT_OPT_PRESOLVE: plane
- * or miss, never fed to a traversal kernel; a stock refill's count when traced).
+ * or miss, never fed to a traversal kernel; a stock refill's count when traced),
+ * out[41] = of out[40], the rays resolved to a miss that adds nothing to their
+ * path and so never written to a ray stream (WPT_OPT_DROP_MISS).
  * Visit/test/byte/iteration counts are only gathered with counting on. */
 int wpt_stats(uint64_t* out, size_t n);
 /* per-kernel device time (profiling on): out[0..11] = {ms, launches} ×
@@ -337,6 +339,9 @@ int wpt_set_lanes(int32_t n);
 #define WPT_OPT_PRESOLVE 37      /* 1 (default): k_generate / k_shade resolve extension rays that provably end on a plane or
                                     in the background (exact root and guard box tests) and keep them out of the traversal
                                     kernels' streams; 0: every ray is traversed. Depth-capped batches on BVH scenes only. */
+#define WPT_OPT_DROP_MISS 38     /* 1 (default): a ray its producer resolves to a miss (WPT_OPT_PRESOLVE) whose throughput *
+                                    background is +0 in every component, the product the next shade would add, is counted
+                                    and written to no stream; 0: it is appended and shaded like any resolved ray */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */

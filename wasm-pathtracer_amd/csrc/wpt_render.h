@@ -99,6 +99,7 @@ struct Stats {
   uint64_t stock_rays = 0;  // rays traced into the stock (they count in rays / shadow_rays when consumed)
   uint64_t stock_rays_used = 0;  // of rays + shadow_rays: those of samples taken from the stock
   uint64_t presolved_rays = 0;   // of rays: resolved by their producer (wpt_presolve.h), never fed to k_extend / k_trace
+  uint64_t dropped_rays = 0;     // of presolved_rays: resolved to a miss that adds nothing, never written to a stream (WPT_OPT_DROP_MISS)
 };
 
 // Kernel-time accumulators (ms), filled when profiling is on.
@@ -134,7 +135,10 @@ struct KernelTimes {
 // Those are the rays the traversal kernels see (the front of a stream). The
 // presolved rays of bounce b (wpt_presolve.h; the back of its stream, from the
 // slice's last entry downward, with their hit records already written) are
-// counted in the 64-bit slot at u32 index kResWord + 2b (low word).
+// counted in the 64-bit slot at u32 index kResWord + 2b (low word). Its high
+// word counts the rays of bounce b that were resolved to a miss adding nothing
+// to their path and dropped (WPT_OPT_DROP_MISS): they are in neither end of
+// the stream, so the device reads the low word only; the host adds both.
 constexpr int kMaxLanes = 8;  // streams made per session (lanes used: nlanes_)
 constexpr uint64_t kMinLanePaths = 1024;  // smaller batches run on one lane
 // after the per-bounce words: rays and shadow rays traced by k_finish (the
@@ -536,6 +540,7 @@ class Renderer {
   int finish_every_ = 4;           // WPT_OPT_FINISH_EVERY: bounces between the RR-only batches' live-count reads
   uint32_t num_guards_ = 0;        // the uploaded scene's guard boxes (0: its rays are never presolved)
   bool presolve_ = true;           // WPT_OPT_PRESOLVE: producers resolve plane-or-miss extension rays (wpt_presolve.h)
+  bool drop_miss_ = true;          // WPT_OPT_DROP_MISS: a ray resolved to a miss that adds nothing is not written to the next stream
   // the presolved count of the stream the next traversal launch belongs to
   // (probing: added to the launch's record, see k_probe_add), or null
   const uint32_t* probe_res_ = nullptr;

@@ -933,12 +933,30 @@ __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t
 }
 
 // The same for a presolving batch: the stream is two-ended (wpt_presolve.h).
-// A block scans its paths' verdicts and reserves both ranges with one atomic
-// instruction (two lanes, two addresses); unresolved rays go to the front
-// (count0), resolved ones to the back, from entry n - 1 downward, with their
-// hit record (t, id) beside them (res0 counts them). The radiance, pixel and
-// rng state of a path stay at its batch index, so the frame does not depend
-// on where its ray lands.
+// Unresolved rays go to the front (count0), resolved ones to the back, from
+// entry n - 1 downward, with their hit record (t, id) beside them (the low
+// word of the 64-bit slot res0 counts them). The radiance, pixel and rng state
+// of a path stay at its batch index, so the frame does not depend on where its
+// ray lands.
+// A block generates kGenTile tiles of kBlock paths, path base + j * kBlock +
+// thread for tile j, keeps direction, rng state, type and verdict of each,
+// scans the kGenTile x kWaves wave counts and reserves both ranges with ONE
+// atomic instruction (two lanes, two addresses, both 64-bit: the word after
+// count0 is unused) per kBlock * kGenTile paths. Within the block the rays keep
+// path order (tile, then wave, then lane), so a wave of bounce 0 still takes
+// neighbouring pixels' rays. kGenTile is 1: 4 and 8 cut the kernel's
+// standalone time on C3 from 6.3 ms to 2.2 and 2.5 ms per step (the two hot
+// counters were the cause), but the 4-lane step, where the kernel runs under
+// the other lanes' traversal, gained nothing (profiles/dropmiss/README.md).
+// A primary ray resolved to a miss is dropped (drop_miss, WPT_OPT_DROP_MISS)
+// when throughput (1) * S.bg is +0 in every component, the product k_shade's
+// miss branch would test: the path keeps only pix_out and col (with
+// stock_slots, the count word of a path that ended after one extension ray),
+// and the ray is counted in the high word of res0 by the same atomic.
+#ifndef WPT_GEN_TILE
+#define WPT_GEN_TILE 1  // tiles per block (experiment builds: 4, 8)
+#endif
+constexpr uint32_t kGenTile = WPT_GEN_TILE;
 __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint32_t* __restrict__ part_pix, uint64_t k0,
                                                         uint32_t n, uint32_t* __restrict__ pix_out,
                                                         float4* __restrict__ thr,
@@ -948,57 +966,95 @@ __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint3
                                                         const uint32_t* __restrict__ rnd_base,
                                                         const uint32_t* __restrict__ rnd_list, uint32_t stock_slots,
                                                         DevScene S, float* __restrict__ t_out,
-                                                        int32_t* __restrict__ id_out, uint32_t* __restrict__ res0) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  constexpr uint32_t kWaves = kBlock / 64;
-  __shared__ uint32_t s_off[2][kWaves];
-  const bool valid = i < n;  // every thread of the block takes part in the scan
-  const GenPath g = gen_path(P, part_pix, k0 + (valid ? i : 0u), rnd_off, rnd_base, rnd_list);
-  float pt;
-  int32_t pid;
-  const bool res = valid && presolve_ray(S, *S.pre, mk(P.cam[0], P.cam[1], P.cam[2]), g.v, pt, pid);
+                                                        int32_t* __restrict__ id_out, uint32_t* __restrict__ res0,
+                                                        uint32_t drop_miss) {
+  constexpr uint32_t kWaves = kBlock / 64, kCols = kGenTile * kWaves;
+  static_assert(kCols < 64, "the scan's totals and the second atomic lane sit in one wave");
+  static_assert(kBlock * kGenTile < 65536u, "a block's resolved and dropped counts share a word");
+  __shared__ uint32_t s_off[2][kCols];
+  const uint32_t base = blockIdx.x * (kBlock * kGenTile);
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t below = (1ull << lane) - 1ull;
-  const uint64_t hm = __ballot(valid && !res), rm = __ballot(res);
-  if (lane == 0) {
-    s_off[0][wid] = (uint32_t)__popcll(hm);
-    s_off[1][wid] = (uint32_t)__popcll(rm);
+  const V3 cam = mk(P.cam[0], P.cam[1], P.cam[2]);
+  const V3 add_c = mulv(mk(1.0f, 1.0f, 1.0f), mk(S.bg[0], S.bg[1], S.bg[2]));  // shade_path's miss branch
+  const bool adds_nothing =
+      drop_miss != 0u && (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+  V3 dir[kGenTile];
+  uint32_t rng[kGenTile], type[kGenTile];
+  float pt[kGenTile];
+  int32_t pid[kGenTile];
+  uint64_t hm[kGenTile], rm[kGenTile];  // the wave's unresolved rays and resolved, stored ones of tile j
+#pragma unroll
+  for (uint32_t j = 0; j < kGenTile; j++) {
+    const uint32_t i = base + j * kBlock + threadIdx.x;
+    const bool valid = i < n;  // every thread of the block takes part in the scan
+    const GenPath g = gen_path(P, part_pix, k0 + (valid ? i : 0u), rnd_off, rnd_base, rnd_list);
+    // the verdict in locals first: with pt[j] / pid[j] passed by reference a
+    // four-tile build kept id's initial -1 for rays that enter the root box
+    float t = 0.0f;
+    int32_t id = -1;
+    const bool res = valid && presolve_ray(S, *S.pre, cam, g.v, t, id);
+    const bool drop = res && id < 0 && adds_nothing;
+    pt[j] = t;
+    pid[j] = id;
+    if (valid) {
+      pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+      // a dropped path of a stock batch ended after one extension ray and no shadow ray
+      col[i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(stock_slots && drop ? 1u : 0u));
+    }
+    dir[j] = g.v;
+    rng[j] = g.s;
+    type[j] = g.type;
+    hm[j] = __ballot(valid && !res);
+    rm[j] = __ballot(res && !drop);
+    const uint64_t dm = __ballot(drop);
+    if (lane == 0) {
+      s_off[0][j * kWaves + wid] = (uint32_t)__popcll(hm[j]);
+      s_off[1][j * kWaves + wid] = (uint32_t)__popcll(rm[j]) | ((uint32_t)__popcll(dm) << 16);
+    }
   }
   __syncthreads();
   if (wid == 0) {
-    const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
+    const uint32_t a = lane < kCols ? s_off[0][lane] : 0u, b = lane < kCols ? s_off[1][lane] : 0u;
     uint32_t ia = a, ib = b;
 #pragma unroll
-    for (uint32_t q = 1; q < kWaves; q <<= 1) {
+    for (uint32_t q = 1; q < kCols; q <<= 1) {
       const uint32_t ya = __shfl_up(ia, q, 64), yb = __shfl_up(ib, q, 64);
       if (lane >= q) { ia += ya; ib += yb; }
     }
-    // lane kWaves - 1 holds both totals; lane kWaves adds the second one
-    const uint32_t tb = (uint32_t)__shfl((int)ib, (int)(kWaves - 1), 64);
-    uint32_t base = 0u;
-    if (lane == kWaves - 1 || lane == kWaves) base = atomicAdd(lane == kWaves - 1 ? count0 : res0, lane == kWaves - 1 ? ia : tb);
-    const uint32_t ba = (uint32_t)__shfl((int)base, (int)(kWaves - 1), 64);
-    const uint32_t bb = (uint32_t)__shfl((int)base, (int)kWaves, 64);
-    if (lane < kWaves) {
+    // lane kCols - 1 holds both totals; lane kCols adds the second one
+    // (resolved and stored in the low word, dropped in the high word)
+    const uint32_t tb = (uint32_t)__shfl((int)ib, (int)(kCols - 1), 64);
+    unsigned long long got = 0ull;
+    if (lane == kCols - 1 || lane == kCols)
+      got = atomicAdd(reinterpret_cast<unsigned long long*>(lane == kCols - 1 ? count0 : res0),
+                      lane == kCols - 1 ? (unsigned long long)ia
+                                        : ((unsigned long long)(tb & 0xffffu) | ((unsigned long long)(tb >> 16) << 32)));
+    const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)got, (int)(kCols - 1), 64);
+    const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)got, (int)kCols, 64);
+    if (lane < kCols) {
       s_off[0][lane] = ba + ia - a;
-      s_off[1][lane] = bb + ib - b;
+      s_off[1][lane] = bb + ((ib - b) & 0xffffu);
     }
   }
   __syncthreads();
-  if (!valid) return;
-  uint32_t p;  // the ray's entry in the stream
-  if (res) {
-    p = n - 1u - (s_off[1][wid] + (uint32_t)__popcll(rm & below));
-    t_out[p] = pt;
-    id_out[p] = pid;
-  } else {
-    p = s_off[0][wid] + (uint32_t)__popcll(hm & below);
+#pragma unroll
+  for (uint32_t j = 0; j < kGenTile; j++) {
+    const bool front = (hm[j] >> lane) & 1ull, back = (rm[j] >> lane) & 1ull;
+    if (!front && !back) continue;  // past the batch's end, or dropped
+    const uint32_t i = base + j * kBlock + threadIdx.x;
+    uint32_t p;  // the ray's entry in the stream
+    if (back) {
+      p = n - 1u - (s_off[1][j * kWaves + wid] + (uint32_t)__popcll(rm[j] & below));
+      t_out[p] = pt[j];
+      id_out[p] = pid[j];
+    } else {
+      p = s_off[0][j * kWaves + wid] + (uint32_t)__popcll(hm[j] & below);
+    }
+    thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(type[j] << kTypeShift));
+    ro[p] = make_float4(cam.x, cam.y, cam.z, __uint_as_float(rng[j]));             // w: the path's rng state
+    rd[p] = make_float4(dir[j].x, dir[j].y, dir[j].z, __uint_as_float(i));      // w: the path's index in the batch
   }
-  pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
-  col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(g.type << kTypeShift));
-  ro[p] = make_float4(P.cam[0], P.cam[1], P.cam[2], __uint_as_float(g.s));  // w: the path's rng state
-  rd[p] = make_float4(g.v.x, g.v.y, g.v.z, __uint_as_float(i));            // w: the path's index in the batch
 }
 
 template <bool TRI_ONLY>
@@ -1221,6 +1277,7 @@ __device__ __forceinline__ void st_hit(float* t, int32_t* id, float tv, int32_t 
 struct ShadeParams {
   int max_depth;
   int debug;
+  int drop_miss;  // WPT_OPT_DROP_MISS (k_shade's presolving variants)
 };
 
 // Dense per-bounce streams of the wavefront. The live paths of bounce b are
@@ -1402,7 +1459,7 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
 }
 
 // Shade kernel: one bounce of the path loop for paths 0..n-1 of the input
-// stream. A block shades 1024 consecutive paths, then appends the survivors
+// stream. A block shades kShadeBlock (256) consecutive paths, then appends the survivors
 // and the shadow rays in path order: one block-wide scan of the two flags and
 // ONE 64-bit atomic add (survivors in the low word, shadow rays in the high
 // word) reserves both output ranges. Blocks append in completion order; a
@@ -1420,6 +1477,13 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
 // hit-record buffers, since this launch still reads t_in / id_in). The third
 // count is reserved in the same scan; its atomic is the same instruction as
 // the append counter's: lanes kWaves-1 and kWaves, two addresses.
+// A ray resolved to a miss is dropped (P.drop_miss) when throughput * S.bg is
+// +0 in every component: that is the product, on the same operands, the next
+// shade_path would test before it returns, so nothing reads the record. A
+// dropped ray goes to neither end of the next stream and is counted in the
+// high word of the presolved slot (the scan carries resolved | dropped << 16
+// per wave, at most 64 each, so the same column and the same atomic serve);
+// with CR it writes the count word the next bounce's end_counts would have.
 // OCT (PNEE): where photon_sample reads the octree: 0 global memory, 1 the
 // child array from LDS, 2 child array and CDFs from LDS (oct_lds_words).
 template <bool TRI_ONLY, bool PNEE, int OCT, bool CR = false, bool PS = false>
@@ -1488,11 +1552,27 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
     if constexpr (PS) {
       if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
     }
+    bool drop = false;
+    if constexpr (PS) {
+      if (res && pid < 0 && P.drop_miss) {
+        const V3 add_c = mulv(ld3(R.th), mk(S.bg[0], S.bg[1], S.bg[2]));  // shade_path's miss branch
+        drop = (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+      }
+      if (drop) {
+        R.alive = res = false;
+        if constexpr (CR) {
+          const uint32_t f = __float_as_uint(R.th.w);
+          reinterpret_cast<uint32_t*>(col + __float_as_uint(R.rd.w))[3] =
+              (((f >> kDepthShift) & kDepthMask) + 1u) | ((f >> kShadowShift) << 16);
+        }
+      }
+    }
     const uint64_t am = __ballot(R.alive && !res), sm = __ballot(R.shadow), rm = PS ? __ballot(res) : 0ull;
+    const uint64_t dm = PS ? __ballot(drop) : 0ull;
     if (lane == 0) {
       s_off[0][wid] = (uint32_t)__popcll(am);
       s_off[1][wid] = (uint32_t)__popcll(sm);
-      if constexpr (PS) s_off[2][wid] = (uint32_t)__popcll(rm);
+      if constexpr (PS) s_off[2][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 16);
     }
     __syncthreads();
     if constexpr (!PS) {
@@ -1531,14 +1611,14 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
       if (lane == kWaves - 1 || lane == kWaves)
         base = atomicAdd(append + (lane == kWaves - 1 ? 0u : off),
                          lane == kWaves - 1 ? ((unsigned long long)ia | ((unsigned long long)ib << 32))
-                                            : (unsigned long long)tc);
+                                            : ((unsigned long long)(tc & 0xffffu) | ((unsigned long long)(tc >> 16) << 32)));
       const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
       const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
       const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
       if (lane < kWaves) {
         s_off[0][lane] = ba + ia - a;
         s_off[1][lane] = bb + ib - b;
-        s_off[2][lane] = bc + ic - c;
+        s_off[2][lane] = bc + ((ic - c) & 0xffffu);
       }
     }
     __syncthreads();
@@ -2102,9 +2182,10 @@ __global__ void __launch_bounds__(kTBlock, TRI_ONLY ? WPT_FINISH_WAVES : 1) k_fi
 // Probing a launch whose stream is two-ended: the rays their producer
 // resolved never reach a wave, so they are added to the first wave's "rays
 // taken" of the bounce's traversal launch; a launch's entries then still sum
-// to the bounce's rays, as the statistics count them. Launched only while
-// the probe records.
-__global__ void k_probe_add(uint4* rec, const uint32_t* __restrict__ res) { rec[0].w += *res; }
+// to the bounce's rays, as the statistics count them: both words of the
+// presolved slot, the resolved rays at the back of the stream and the dropped
+// ones (WPT_OPT_DROP_MISS). Launched only while the probe records.
+__global__ void k_probe_add(uint4* rec, const uint32_t* __restrict__ res) { rec[0].w += res[0] + res[1]; }
 
 // Test hook: presolve_ray (wpt_presolve.h) as the producers run it, over
 // caller-given rays (6 floats each: origin, direction).
@@ -2647,6 +2728,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 35: if (!range(0, 1)) return false; stock_prefill_ = v != 0; return true;
     case 36: if (!range(0, (int64_t)1 << 40)) return false; async_fused_below_ = (uint64_t)v; return true;
     case 37: if (!range(0, 1)) return false; presolve_ = v != 0; return true;
+    case 38: if (!range(0, 1)) return false; drop_miss_ = v != 0; return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -2699,6 +2781,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 35: v = stock_prefill_ ? 1 : 0; return true;
     case 36: v = (int64_t)async_fused_below_; return true;
     case 37: v = presolve_ ? 1 : 0; return true;
+    case 38: v = drop_miss_ ? 1 : 0; return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -2957,10 +3040,13 @@ static void add_counts(Stats& st, const uint32_t* hc, int b, bool stock, bool pr
   for (int i = 0; i < b; i++) {
     // the rays k_extend / k_trace saw plus those their producer resolved
     // (a batch that presolves nothing neither clears nor copies those words)
-    const uint32_t res = presolve ? hc[kResWord + 2 * i] : 0u;
+    // the slot's high word: of the resolved ones, those dropped (in no stream)
+    const uint32_t drop = presolve ? hc[kResWord + 2 * i + 1] : 0u;
+    const uint64_t res = (uint64_t)(presolve ? hc[kResWord + 2 * i] : 0u) + drop;
     r += (i == 0 ? hc[0] : hc[2 + 2 * (i - 1)]) + res;
     sr += hc[3 + 2 * i];
     st.presolved_rays += res;  // (a stock batch's too, when traced)
+    st.dropped_rays += drop;
   }
   r += hc[kFinishWord];
   sr += hc[kFinishWord + 1];
@@ -3033,9 +3119,10 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
     HIP_OK(hipMemsetAsync(d_counts_, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), ks_));
     if (B.presolve)
       LAUNCH_TIMED(0, generate, n_generate,
-                   k_generate_ps<<<blocks_for(nn), kBlock, 0, ks_>>>(
+                   k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, ks_>>>(
                        G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0], p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off,
-                       rnd_base, B.mlist, slots, ds_, p_t_, p_id_, reinterpret_cast<uint32_t*>(res_ctr(0))));
+                       rnd_base, B.mlist, slots, ds_, p_t_, p_id_, reinterpret_cast<uint32_t*>(res_ctr(0)),
+                       drop_miss_ ? 1u : 0u));
     else
       LAUNCH_TIMED(0, generate, n_generate,
                    k_generate<<<blocks_for(nn), kBlock, 0, ks_>>>(G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0],
@@ -3059,7 +3146,7 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
 // of an RR-only batch must come back first. block: wait for such counts;
 // else return with B in kCountWait when they have not landed yet.
 bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
-  const ShadeParams SP{max_depth_, debug_};
+  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0};
   // the bound lane's paths of stream rin, to their end, one lane each
   auto launch_finish = [&](const RayStream& rin, int bb, uint32_t g, bool pn) -> bool {
 #define WPT_FIN(T, PN, CR) \
