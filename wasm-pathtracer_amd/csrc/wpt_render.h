@@ -127,7 +127,9 @@ struct KernelTimes {
 // Per path of the slice: the ray streams of two consecutive bounces (ping-
 // pong: bounce b reads ray[b & 1], its survivors are appended to
 // ray[(b + 1) & 1]), the hit record of bounce b's rays, the shadow stream of
-// one bounce, and the radiance (and pixel) at the path's batch index.
+// one bounce, and the radiance (and pixel) at the path's batch index. Nothing
+// aliases these buffers: a launch reaches them through its LaunchCtx (below),
+// so reallocating a lane's buffers needs no refresh anywhere else.
 //
 // counts (u32): [0] = bounce 0's ray count (k_generate), then per bounce b a
 // 64-bit append counter at u32 index 2 + 2b: low word = rays of bounce b + 1,
@@ -168,8 +170,18 @@ struct PathSet {
   float4 *so = nullptr, *sd = nullptr, *sc = nullptr;
   uint32_t* counts = nullptr;    // kCountWords, see above
   uint32_t* h_counts = nullptr;  // pinned mirror
-  uint2* spill = nullptr;
+  uint2* spill = nullptr;       // traversal-stack spill (entries beyond the LDS slots)
   size_t spill_cap = 0;
+  float* hit_t(int k) const { return k ? t1 : t; }
+  int32_t* hit_id(int k) const { return k ? id1 : id; }
+  // count words: rays of bounce b, shadow rays of bounce b, k_shade's append
+  // counter of bounce b
+  uint32_t* ext_count(int b) const { return b == 0 ? counts : counts + 2 + 2 * (b - 1); }
+  uint32_t* sh_count(int b) const { return counts + 3 + 2 * b; }
+  unsigned long long* append_ctr(int b) const { return reinterpret_cast<unsigned long long*>(counts + 2 + 2 * b); }
+  // presolved rays of bounce b's stream (k_shade finds them from append_ctr:
+  // res_ctr(b + 1) = append_ctr(b) + kResWord / 2)
+  unsigned long long* res_ctr(int b) const { return reinterpret_cast<unsigned long long*>(counts + kResWord + 2 * b); }
 };
 
 // One batch of the wavefront in flight: its path mapping, its lanes and how
@@ -211,6 +223,25 @@ struct Batch {
   hipEvent_t live[kMaxLanes] = {};  // async RR-only: the live count landed in hl
   uint32_t* hc = nullptr;           // async: pinned nl x kCountWords, the final counts
   uint32_t* hl = nullptr;           // async: pinned nl live-count words
+};
+
+// Where and how one launch runs, passed down to the launchers: made per
+// (batch, lane, bounce) by Renderer::batch_ctx, or for lane 0 alone by
+// Renderer::lane0_ctx (the test hooks and the photon build).
+struct LaunchCtx {
+  int lane = 0;
+  const PathSet* ps = nullptr;   // lanes_[lane]
+  hipStream_t stream = nullptr;  // the lane's, or its low-priority one (async batches with WPT_OPT_ASYNC_PRIO)
+  bool async = false;            // the launch belongs to an async batch ...
+  uint64_t paths = 0;            // ... of this many paths in the lane's slice
+  int batch_lanes = 1;           // lanes of the batch (1: full-capacity traversal grids)
+  bool timed = false;            // LAUNCH_TIMED: the main lanes' launches when profiling
+  bool count = false;            // the kernels' work-counting variants
+  int bounce = 0;
+  int hit_sel = 0;               // the hit-record buffers a traversal launch writes (bounce & 1 when presolving)
+  // the presolved count of the bounce's stream (probing: added to the
+  // launch's record, see k_probe_add), or null
+  const uint32_t* probe_res = nullptr;
 };
 
 class Renderer {
@@ -313,7 +344,8 @@ class Renderer {
   bool ensure_paths(uint64_t n, std::string& err);   // lane 0 holds >= n paths
   bool ensure_lane(int i, uint64_t n, std::string& err);
   void free_lane_paths(PathSet& L);
-  void bind_lane(int i);  // the p_*/q_/s_* views, counts, spill and kernel stream ks_ = lane i's
+  LaunchCtx batch_ctx(const Batch& B, int i, int b) const;  // slice i of B at bounce b
+  LaunchCtx lane0_ctx(bool count) const;                     // lane 0 alone, untimed
   // half < 0: progressive paths k0.. over the partition; half 0/1: positions
   // k0.. of that screen half's current sample round
   bool run_batch(uint64_t k0, uint64_t n, int half, std::string& err, const uint32_t* part_pix = nullptr,
@@ -340,13 +372,13 @@ class Renderer {
   bool exchange_frame(std::string& err);
   bool plan_slice(int h, uint64_t a, uint64_t b, uint64_t& local, std::string& err);
   void free_rounds();
-  bool launch_extend(const float4* ro, const float4* rd, const uint32_t* cnt, std::string& err);
-  bool launch_shadow(const uint32_t* cnt, uint8_t* occ_out, std::string& err);
-  bool launch_trace(int b, std::string& err);
+  bool launch_extend(const LaunchCtx& C, const float4* ro, const float4* rd, const uint32_t* cnt, std::string& err);
+  bool launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* occ_out, std::string& err);
+  bool launch_trace(const LaunchCtx& C, std::string& err);
   bool size_grids(std::string& err);
   uint32_t max_grid() const;
   size_t spill_slots() const;
-  uint32_t spill_grid() const;
+  uint32_t spill_grid(const PathSet& L) const;
   bool ensure_spill(int l, uint32_t grid, std::string& err);
   // one-shot grid of a slice of `paths` (fused: 2 rays per path), its spill
   // area capped at 1 GiB (beyond it the grid is clamped: partly persistent)
@@ -431,8 +463,8 @@ class Renderer {
   uint32_t refill_id_ = 0;            // ids of the session's refills, in issue order
   int refill_lane_ = 0;               // the stock lane of the next refill
   uint32_t round_need_[2] = {0, 0};   // per half: 1 + the refill its current round's samples wait for (0: none)
-  bool stock_redo_[2] = {false, false};
-  int log_ = 0;  // WPT_OPT_LOG: host steps of the adaptive rounds and async lanes to stderr (debugging)  // per half: the stock was dropped while its round was partly added
+  bool stock_redo_[2] = {false, false};  // per half: the stock was dropped while its round was partly added
+  int log_ = 0;  // WPT_OPT_LOG: host steps of the adaptive rounds and async lanes to stderr (debugging)
   bool stock_active(int h) const { return stock_slots_ != 0 && nranks_ == 1 && adaptive_[h]; }
   bool stock_alloc(std::string& err);
   void stock_drop();                     // forget the ring (reset, reallocation)
@@ -446,8 +478,6 @@ class Renderer {
   bool refill_issue(Refill& F, int h, uint64_t wt, std::string& err);
   bool stock_prefill(int h, uint64_t budget, std::string& err);  // at a compute call's start
   bool stock_prefill_ = true;  // WPT_OPT_STOCK_PREFILL
-  bool pend_presolve_ = false;           // ... presolved (its presolved counts were cleared and copied)
-  bool pend_stock_ = false;              // the last main batch traced stock samples (its rays count when consumed)
   std::deque<Batch*> aq_[2];  // per queue: async batches not yet fully issued, in order
   // A random half's whole rounds traced beside the adaptive half's rounds
   // (WPT_OPT_FILL, compute_halves): its pixels outside the seam (the two
@@ -460,7 +490,6 @@ class Renderer {
   // same-session (profiles/r06/ab_async_fused_grid.jsonl)
   int async_grid_pct_ = 100;  // WPT_OPT_ASYNC_GRID_PCT: their traversal grids, % of resident capacity (0: the main batches')
   uint64_t async_fused_below_ = 1ull << 26;  // WPT_OPT_ASYNC_FUSED_BELOW: async batches below this many paths run fused (0: fused_below)
-  bool async_launch_ = false;  // the launch being issued belongs to an async batch
   uint32_t* d_seam_pix_[2] = {nullptr, nullptr};
   uint32_t* d_rest_pix_[2] = {nullptr, nullptr};
   uint32_t seam_npix_[2] = {0, 0}, rest_npix_[2] = {0, 0};
@@ -480,15 +509,12 @@ class Renderer {
   // kTBlock of the most rays the launch can see (rays_per_path x the slice):
   // every wave takes at most one feed chunk, so its blocks retire as soon
   // as their rays end and free the CUs for the main lanes' next kernel
-  uint32_t async_grid(uint32_t g, int base_pct, uint32_t rays_per_path = 1) const {
-    if (!async_launch_) return g;
-    if (async_oneshot_) return std::max<uint32_t>(1u, (uint32_t)((async_paths_ * rays_per_path + 255) / 256));
+  uint32_t async_grid(const LaunchCtx& C, uint32_t g, int base_pct, uint32_t rays_per_path = 1) const {
+    if (!C.async) return g;
+    if (async_oneshot_) return std::max<uint32_t>(1u, (uint32_t)((C.paths * rays_per_path + 255) / 256));
     return async_grid_pct_ > 0 ? std::max<uint32_t>(1u, (uint32_t)((uint64_t)g * async_grid_pct_ / base_pct)) : g;
   }
   bool async_oneshot_ = false;  // WPT_OPT_ASYNC_ONESHOT
-  uint64_t async_paths_ = 0;    // paths of the bound async slice
-  void bind_batch_lane(const Batch& B, int l);  // bind_lane(l), on the async stream for async batches
-  bool time_launches_ = false;  // LAUNCH_TIMED: the main lanes' launches when profiling
   uint8_t* d_samp_ = nullptr;       // sampling visualisation RGBA8 (allocated with the viewport)
   ExchangeFn xfn_ = nullptr;
   void* xuser_ = nullptr;
@@ -507,8 +533,6 @@ class Renderer {
 
   int device_ = -1;
   int ncu_ = 256;
-  uint2* d_spill_ = nullptr;       // traversal-stack spill (entries beyond the LDS slots)
-  size_t spill_cap_ = 0;
   // persistent grids per kernel variant (tri_only + 2 count + 4 traversal):
   // [0..7] multi-lane batches (grid_pct_ of the resident capacity), [8..15]
   // one-lane batches (all of it); k_trace: tri_only + 2 count
@@ -541,27 +565,23 @@ class Renderer {
   uint32_t num_guards_ = 0;        // the uploaded scene's guard boxes (0: its rays are never presolved)
   bool presolve_ = true;           // WPT_OPT_PRESOLVE: producers resolve plane-or-miss extension rays (wpt_presolve.h)
   bool drop_miss_ = true;          // WPT_OPT_DROP_MISS: a ray resolved to a miss that adds nothing is not written to the next stream
-  // the presolved count of the stream the next traversal launch belongs to
-  // (probing: added to the launch's record, see k_probe_add), or null
-  const uint32_t* probe_res_ = nullptr;
-  int hit_sel_ = 0;                // the hit-record buffers the next traversal launch writes (bounce & 1)
-  int batch_lanes_ = 1;            // lanes of the batch being launched (1: full-capacity traversal grids)
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
   uint32_t probe_cap_ = 0, probe_waves_ = 0, probe_used_ = 0;
   uint4* d_probe_ = nullptr;
   std::vector<uint32_t> probe_meta_;
-  int cur_bounce_ = 0;
-  uint4* probe_slot(int kernel, uint32_t grid);
+  uint4* probe_slot(const LaunchCtx& C, int kernel, uint32_t grid);
   uint32_t* d_fallback_ = nullptr; // [2] rays re-traced exactly (extend, shadow)
   hipStream_t stream_ = nullptr;
-  hipStream_t ks_ = nullptr;       // stream of the bound lane (kernel launches of a batch)
   PathSet lanes_[kMaxLanes];
   int lanes_made_ = 0;
-  bool stats_pending_ = false;     // the last batch's counts not yet read (flush_counts)
+  // the last main batch, until flush_counts reads its counts: its lanes and
+  // bounces; it traced stock samples (its rays count when consumed); it
+  // presolved (its presolved counts were cleared and copied)
+  bool stats_pending_ = false;
   int pend_nl_ = 0, pend_b_ = 0;
+  bool pend_stock_ = false, pend_presolve_ = false;
   int nlanes_ = 4;                 // wpt_set_lanes (1..kMaxLanes); 4 with half-GPU traversal grids (C3 +4.5 % over 3 lanes at full grids)
-  int bound_ = 0;
   hipEvent_t ev_main_ = nullptr;   // lanes > 0 wait for the main stream's prior work
   hipEvent_t ev_ref_ = nullptr;    // profiling: time origin of a batch's launch intervals
   std::vector<void*> scene_bufs_;
@@ -588,35 +608,8 @@ class Renderer {
   uint32_t* d_cnt_ = nullptr;
   uint8_t* d_rgba_ = nullptr;
 
-  // streams of the bound lane (views into lanes_[bound_]; cap_ = that lane's
-  // capacity)
-  uint64_t cap_ = 0;
-  uint32_t* p_pixel_ = nullptr;
-  float4* p_col_ = nullptr;
-  float4* p_ro_[2] = {nullptr, nullptr};
-  float4* p_rd_[2] = {nullptr, nullptr};
-  float4* p_thr_[2] = {nullptr, nullptr};
-  float* p_t_ = nullptr;
-  int32_t* p_id_ = nullptr;
-  float* p_t1_ = nullptr;
-  int32_t* p_id1_ = nullptr;
-  float* hit_t(int k) const { return k ? p_t1_ : p_t_; }
-  int32_t* hit_id(int k) const { return k ? p_id1_ : p_id_; }
-  float4* s_o_ = nullptr;
-  float4* s_d_ = nullptr;
-  float4* s_c_ = nullptr;
-  uint32_t* d_counts_ = nullptr;   // kCountWords (PathSet::counts)
   unsigned long long* d_work_ = nullptr;  // [kWorkCopies][kWorkWords] extend visits/tests/node bytes, shadow visits/tests/node bytes, ...
-  uint32_t* h_counts_ = nullptr;   // pinned mirror
   uint32_t* h_word_ = nullptr;     // pinned scratch of the round planning (a round's path count)
-  // count words of the bound lane: rays of bounce b, shadow rays of bounce b,
-  // k_shade's append counter of bounce b
-  uint32_t* ext_count(int b) const { return b == 0 ? d_counts_ : d_counts_ + 2 + 2 * (b - 1); }
-  uint32_t* sh_count(int b) const { return d_counts_ + 3 + 2 * b; }
-  unsigned long long* append_ctr(int b) const { return reinterpret_cast<unsigned long long*>(d_counts_ + 2 + 2 * b); }
-  // presolved rays of bounce b's stream (k_shade finds them from append_ctr:
-  // res_ctr(b + 1) = append_ctr(b) + kResWord / 2)
-  unsigned long long* res_ctr(int b) const { return reinterpret_cast<unsigned long long*>(d_counts_ + kResWord + 2 * b); }
 
   bool counting_ = false;
   bool profiling_ = false;

@@ -2431,7 +2431,6 @@ bool Renderer::set_device(int dev, std::string& err) {
     HIP_OK(hipMalloc(&L.counts, sizeof(uint32_t) * kCountWords));
     HIP_OK(hipHostMalloc(&L.h_counts, sizeof(uint32_t) * kCountWords));
   }
-  bind_lane(0);
   HIP_OK(hipMalloc(&d_work_, sizeof(unsigned long long) * kWorkWords * kWorkCopies));
   HIP_OK(hipMalloc(&d_fallback_, sizeof(uint32_t) * 4));  // [0..1] fallbacks, [2] stack overflow
   HIP_OK(hipMemset(d_fallback_, 0, sizeof(uint32_t) * 4));
@@ -2461,27 +2460,6 @@ void Renderer::free_lane_paths(PathSet& L) {
 
 void Renderer::free_paths() {
   for (PathSet& L : lanes_) free_lane_paths(L);
-  bind_lane(bound_);
-}
-
-void Renderer::bind_lane(int i) {
-  const PathSet& L = lanes_[i];
-  bound_ = i;
-  async_launch_ = false;
-  ks_ = L.stream;
-  cap_ = L.cap;
-  p_pixel_ = L.pixel;
-  p_col_ = L.col;
-  for (int k = 0; k < 2; k++) {
-    p_ro_[k] = L.ro[k];
-    p_rd_[k] = L.rd[k];
-    p_thr_[k] = L.thr[k];
-  }
-  p_t_ = L.t; p_id_ = L.id;
-  p_t1_ = L.t1; p_id1_ = L.id1;
-  s_o_ = L.so; s_d_ = L.sd; s_c_ = L.sc;
-  d_counts_ = L.counts; h_counts_ = L.h_counts;
-  d_spill_ = L.spill; spill_cap_ = L.spill_cap;
 }
 
 bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
@@ -2921,7 +2899,6 @@ bool Renderer::ensure_lane(int i, uint64_t n, std::string& err) {
     const size_t need = spill_slots() * (size_t)std::max<uint32_t>(max_grid(), 1) * kTBlock;
     HIP_OK(hipMalloc(&L.spill, need * sizeof(uint2)));
     L.spill_cap = need;
-    if (i == bound_) bind_lane(i);
   }
   if (async_prio_ && i >= kAsyncLane0 && !L.lo) {
     // async batches' low-priority stream (WPT_OPT_ASYNC_PRIO)
@@ -2947,23 +2924,23 @@ bool Renderer::ensure_lane(int i, uint64_t n, std::string& err) {
   HIP_OK(hipMalloc(&L.sd, 16 * n));
   HIP_OK(hipMalloc(&L.sc, 16 * n));
   L.cap = n;
-  bind_lane(bound_);
   return true;
 }
 
 bool Renderer::ensure_paths(uint64_t n, std::string& err) { return ensure_lane(0, n, err); }
 
-#define LAUNCH_TIMED(slot, accum, counter, ...)                          \
+// A launch of context C (its `timed` and `stream`), its interval recorded.
+#define LAUNCH_TIMED(C, slot, accum, counter, ...)                       \
   do {                                                                   \
     hipEvent_t a_ = nullptr, b_ = nullptr;                               \
-    if (time_launches_) {                                                \
+    if ((C).timed) {                                                     \
       if (!next_event(&a_, err) || !next_event(&b_, err)) return false;  \
-      HIP_OK(hipEventRecord(a_, ks_));                                   \
+      HIP_OK(hipEventRecord(a_, (C).stream));                            \
     }                                                                    \
     __VA_ARGS__;                                                         \
     HIP_OK(hipGetLastError());                                           \
-    if (time_launches_) {                                                \
-      HIP_OK(hipEventRecord(b_, ks_));                                   \
+    if ((C).timed) {                                                     \
+      HIP_OK(hipEventRecord(b_, (C).stream));                            \
       pending_.push_back(PendingTiming{a_, b_, slot});                   \
     }                                                                    \
   } while (0)
@@ -3074,7 +3051,6 @@ void Renderer::batch_counts(const Batch& B, const uint32_t* hc) {
 // Lanes, slices and bounce 0 of batch B (k_generate on each lane's stream,
 // after the main stream's work so far: reset, round planning, k_spec_plan).
 bool Renderer::batch_begin(Batch& B, std::string& err) {
-  time_launches_ = profiling_ && !B.async;
   // the mapping: an explicit one (stock batches), half h's current round,
   // or paths k0 .. k0+n-1 of the sequence path k -> (pixel list[k % npix],
   // sample k / npix) over this rank's pixels or over `part` (a screen half)
@@ -3098,36 +3074,37 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   // RR-only batches (the k_finish hand-over reads one live count per lane)
   // run without the presolve
   B.presolve = presolve_ && max_depth_ > 0 && num_guards_ != 0;
-  if (time_launches_) HIP_OK(hipEventRecord(ev_ref_, stream_));
+  if (profiling_ && !B.async) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
-  batch_lanes_ = B.nl;
   for (int i = 0; i < B.nl; i++) {
     const int l = B.lane0 + i;
-    if (B.presolve && !lanes_[l].t1 && lanes_[l].cap) {
+    PathSet& L = lanes_[l];
+    if (B.presolve && !L.t1 && L.cap) {
       // the second pair of hit records, made with the lane's first presolving
       // batch: sessions that presolve nothing allocate what they did before
-      HIP_OK(hipMalloc(&lanes_[l].t1, 4 * lanes_[l].cap));
-      HIP_OK(hipMalloc(&lanes_[l].id1, 4 * lanes_[l].cap));
+      HIP_OK(hipMalloc(&L.t1, 4 * L.cap));
+      HIP_OK(hipMalloc(&L.id1, 4 * L.cap));
     }
-    bind_batch_lane(B, l);
-    if (B.off[i + 1] - B.off[i] > cap_) { bind_lane(0); err = "batch exceeds lane capacity"; return false; }
-    if (l != 0) HIP_OK(hipStreamWaitEvent(ks_, ev_main_, 0));  // after reset / round planning on the main stream
+    const LaunchCtx C = batch_ctx(B, i, 0);
+    const hipStream_t s = C.stream;
+    if (C.paths > L.cap) { err = "batch exceeds lane capacity"; return false; }
+    if (l != 0) HIP_OK(hipStreamWaitEvent(s, ev_main_, 0));  // after reset / round planning on the main stream
     // a low-priority stream after the lane's last main batch (its buffers)
-    if (ks_ != lanes_[l].stream) HIP_OK(hipStreamWaitEvent(ks_, lanes_[l].done, 0));
-    const uint32_t nn = (uint32_t)(B.off[i + 1] - B.off[i]);
+    if (s != L.stream) HIP_OK(hipStreamWaitEvent(s, L.done, 0));
+    const uint32_t nn = (uint32_t)C.paths;
     // (the presolved counts, the words from kResWord on, only where they are used)
-    HIP_OK(hipMemsetAsync(d_counts_, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), ks_));
+    HIP_OK(hipMemsetAsync(L.counts, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), s));
     if (B.presolve)
-      LAUNCH_TIMED(0, generate, n_generate,
-                   k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, ks_>>>(
-                       G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0], p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off,
-                       rnd_base, B.mlist, slots, ds_, p_t_, p_id_, reinterpret_cast<uint32_t*>(res_ctr(0)),
+      LAUNCH_TIMED(C, 0, generate, n_generate,
+                   k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, s>>>(
+                       G, part, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, rnd_off,
+                       rnd_base, B.mlist, slots, ds_, L.t, L.id, reinterpret_cast<uint32_t*>(L.res_ctr(0)),
                        drop_miss_ ? 1u : 0u));
     else
-      LAUNCH_TIMED(0, generate, n_generate,
-                   k_generate<<<blocks_for(nn), kBlock, 0, ks_>>>(G, part, B.k0 + B.off[i], nn, p_pixel_, p_thr_[0],
-                                                                p_col_, p_ro_[0], p_rd_[0], d_counts_, rnd_off, rnd_base,
-                                                                B.mlist, slots));
+      LAUNCH_TIMED(C, 0, generate, n_generate,
+                   k_generate<<<blocks_for(nn), kBlock, 0, s>>>(G, part, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col,
+                                                              L.ro[0], L.rd[0], L.counts, rnd_off, rnd_base, B.mlist,
+                                                              slots));
   }
   B.maxb = max_depth_ > 0 ? std::min(max_depth_, kMaxBounces) : kMaxBounces;
   // fused: bounce b >= 1 traces its extension rays together with bounce b-1's
@@ -3138,7 +3115,6 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   B.b = 0;
   B.finished = false;
   B.state = Batch::kBouncing;
-  bind_lane(0);
   return true;
 }
 
@@ -3147,10 +3123,12 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
 // else return with B in kCountWait when they have not landed yet.
 bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
   const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0};
-  // the bound lane's paths of stream rin, to their end, one lane each
-  auto launch_finish = [&](const RayStream& rin, int bb, uint32_t g, bool pn) -> bool {
-#define WPT_FIN(T, PN, CR) \
-  k_finish<T, PN, CR><<<g, kTBlock, 0, ks_>>>(ds_, SP, rin, ext_count(bb + 1), p_col_, d_spill_, d_counts_ + kFinishWord)
+  // the paths of C's lane in stream rin, to their end, one lane each
+  auto launch_finish = [&](const LaunchCtx& C, const RayStream& rin, uint32_t g, bool pn) -> bool {
+    const PathSet& L = *C.ps;
+#define WPT_FIN(T, PN, CR)                                                                                 \
+  k_finish<T, PN, CR><<<g, kTBlock, 0, C.stream>>>(ds_, SP, rin, L.ext_count(C.bounce + 1), L.col, L.spill, \
+                                                  L.counts + kFinishWord)
 #define WPT_FIN2(T, PN) \
   if (B.stock) WPT_FIN(T, PN, true); \
   else WPT_FIN(T, PN, false)
@@ -3167,8 +3145,6 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
     return true;
   };
   while (B.state == Batch::kBouncing || B.state == Batch::kCountWait) {
-    time_launches_ = profiling_ && !B.async;
-    batch_lanes_ = B.nl;
     if (B.state == Batch::kCountWait) {
       // the live counts of bounce b = B.b - 1 (RR-only batches): stop once
       // every lane's stream drains; once few paths are left, k_finish runs
@@ -3189,12 +3165,8 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
       } else {
         // the main lanes wait here: first let the async lanes' batches go on
         if (async_pending() && !pump(false, err)) return false;
-        time_launches_ = profiling_;
-        batch_lanes_ = B.nl;
         for (int i = 0; i < B.nl; i++)
           if (!host_wait_stream(lanes_[B.lane0 + i].stream, err)) return false;
-        time_launches_ = profiling_;  // (the waits pump the async lanes)
-        batch_lanes_ = B.nl;
         for (int i = 0; i < B.nl; i++) live[i] = lanes_[B.lane0 + i].h_counts[0];
       }
       for (int i = 0; i < B.nl; i++) left += live[i];
@@ -3202,17 +3174,18 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
       if (left == 0) break;
       if (left <= finish_below_ && b + 1 < B.maxb) {
         for (int i = 0; i < B.nl; i++) {
-          bind_batch_lane(B, B.lane0 + i);
+          const LaunchCtx C = batch_ctx(B, i, b);
+          const PathSet& L = *C.ps;
           // bounce b's shadow rays first (fused mode traces them with the
           // next bounce): they are the paths' next colour additions
-          if (B.fused && !launch_shadow(sh_count(b), nullptr, err)) { bind_lane(0); return false; }
+          if (B.fused && !launch_shadow(C, L.sh_count(b), nullptr, err)) return false;
           if (live[i] == 0) continue;
-          const RayStream rin{p_ro_[(b + 1) & 1], p_rd_[(b + 1) & 1], p_thr_[(b + 1) & 1]};
+          const RayStream rin{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
           const uint32_t g =
               (uint32_t)std::min<uint64_t>((live[i] + kTBlock - 1) / kTBlock,
-                                           std::min(async_grid(grid_tr_[ds_.tri_only ? 1 : 0], trace_grid_pct_),
-                                                    spill_grid()));
-          if (!launch_finish(rin, b, g, B.pnee)) { bind_lane(0); return false; }
+                                           std::min(async_grid(C, grid_tr_[ds_.tri_only ? 1 : 0], trace_grid_pct_),
+                                                    spill_grid(L)));
+          if (!launch_finish(C, rin, g, B.pnee)) return false;
         }
         B.finished = true;
         break;
@@ -3221,23 +3194,18 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
     }
     if (B.b >= B.maxb) break;
     const int b = B.b;
-    cur_bounce_ = b;
     for (int i = 0; i < B.nl; i++) {
-      bind_batch_lane(B, B.lane0 + i);
-      const uint32_t nn = (uint32_t)(B.off[i + 1] - B.off[i]);
-      // (batches that presolve nothing keep one pair of hit-record buffers, as before)
-      const int hs = B.presolve ? (b & 1) : 0;
-      hit_sel_ = hs;
-      probe_res_ = B.presolve ? reinterpret_cast<const uint32_t*>(res_ctr(b)) : nullptr;
-      const bool traced = (B.fused && b > 0) ? launch_trace(b, err)
-                                             : launch_extend(p_ro_[b & 1], p_rd_[b & 1], ext_count(b), err);
-      hit_sel_ = 0;
-      probe_res_ = nullptr;
-      if (!traced) { bind_lane(0); return false; }
+      const LaunchCtx C = batch_ctx(B, i, b);
+      const PathSet& L = *C.ps;
+      const uint32_t nn = (uint32_t)C.paths;
+      const int hs = C.hit_sel;
+      const bool traced = (B.fused && b > 0) ? launch_trace(C, err)
+                                             : launch_extend(C, L.ro[b & 1], L.rd[b & 1], L.ext_count(b), err);
+      if (!traced) return false;
       {
-        const RayStream in{p_ro_[b & 1], p_rd_[b & 1], p_thr_[b & 1]};
-        const RayStream out{p_ro_[(b + 1) & 1], p_rd_[(b + 1) & 1], p_thr_[(b + 1) & 1]};
-        const ShadowStream sh{s_o_, s_d_, s_c_};
+        const RayStream in{L.ro[b & 1], L.rd[b & 1], L.thr[b & 1]};
+        const RayStream out{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
+        const ShadowStream sh{L.so, L.sd, L.sc};
         [[maybe_unused]] const uint32_t sgrid =
             std::max<uint32_t>(1, std::min<uint32_t>((nn + kShadeBlock - 1) / kShadeBlock, grid_shade_));
         // the persistent grid of the variant launched: its own occupancy
@@ -3260,12 +3228,11 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
 #define WPT_SHADE1(T, PN, OC, CR, PS)                                                                               \
   do {                                                                                                              \
     WPT_SHADE_GRID(T, PN, OC, CR, PS)                                                                               \
-    const uint32_t sgo = async_launch_ && async_oneshot_ ? std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock) \
-                                                         : sg;                                                      \
-    LAUNCH_TIMED(2, shade, n_shade,                                                                                 \
-                 k_shade<T, PN, OC, CR, PS><<<sgo, kShadeBlock, OC ? 4 * ds_.oct_lds_words : 0, ks_>>>(             \
-                     ds_, SP, in, out, sh, p_col_, ext_count(b), hit_t(hs), hit_id(hs), append_ctr(b),             \
-                     hit_t(hs ^ 1), hit_id(hs ^ 1), nn));                                                           \
+    const uint32_t sgo = C.async && async_oneshot_ ? std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock) : sg; \
+    LAUNCH_TIMED(C, 2, shade, n_shade,                                                                              \
+                 k_shade<T, PN, OC, CR, PS><<<sgo, kShadeBlock, OC ? 4 * ds_.oct_lds_words : 0, C.stream>>>(        \
+                     ds_, SP, in, out, sh, L.col, L.ext_count(b), L.hit_t(hs), L.hit_id(hs), L.append_ctr(b),      \
+                     L.hit_t(hs ^ 1), L.hit_id(hs ^ 1), nn));                                                       \
   } while (0)
 // a stock batch's paths write their ray counts (CR)
 #define WPT_SHADE(T, PN, OC)              \
@@ -3293,37 +3260,31 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
 #undef WPT_SHADE1
 #undef WPT_SHADE_GRID
       }
-      if (!B.fused && !launch_shadow(sh_count(b), nullptr, err)) { bind_lane(0); return false; }
+      if (!B.fused && !launch_shadow(C, L.sh_count(b), nullptr, err)) return false;
     }
     B.b = b + 1;
     if (max_depth_ <= 0 && (b % finish_every_) == finish_every_ - 1) {
       // RR-only mode: the live count of every lane comes back to the host
       for (int i = 0; i < B.nl; i++) {
-        bind_batch_lane(B, B.lane0 + i);
-        if (B.async) {
-          HIP_OK(hipMemcpyAsync(B.hl + i, ext_count(b + 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ks_));
-          HIP_OK(hipEventRecord(B.live[i], ks_));
-        } else {
-          HIP_OK(hipMemcpyAsync(h_counts_, ext_count(b + 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ks_));
-        }
+        const LaunchCtx C = batch_ctx(B, i, b);
+        const PathSet& L = *C.ps;
+        uint32_t* dst = B.async ? B.hl + i : L.h_counts;
+        HIP_OK(hipMemcpyAsync(dst, L.ext_count(b + 1), sizeof(uint32_t), hipMemcpyDeviceToHost, C.stream));
+        if (B.async) HIP_OK(hipEventRecord(B.live[i], C.stream));
       }
       B.state = Batch::kCountWait;
     }
   }
-  bind_lane(0);
   return batch_tail(B, err);
 }
 
 // B's last shadow rays (fused), its accumulation (or, for a speculated batch,
 // the radiance into its slot) and its count words; B is then issued.
 bool Renderer::batch_tail(Batch& B, std::string& err) {
-  time_launches_ = profiling_ && !B.async;
-  batch_lanes_ = B.nl;
-  cur_bounce_ = B.b;
   if (B.fused && B.b > 0 && !B.finished) {
     for (int i = 0; i < B.nl; i++) {  // the last bounce's shadow rays
-      bind_batch_lane(B, B.lane0 + i);
-      if (!launch_shadow(sh_count(B.b - 1), nullptr, err)) { bind_lane(0); return false; }
+      const LaunchCtx C = batch_ctx(B, i, B.b);
+      if (!launch_shadow(C, C.ps->sh_count(B.b - 1), nullptr, err)) return false;
     }
   }
   const bool round = B.half >= 0 && !B.moff;
@@ -3334,26 +3295,27 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
   // stock batch stores each path into its ring slot instead
   for (int i = 0; i < B.nl; i++) {
     const int l = B.lane0 + i;
-    bind_batch_lane(B, l);
-    const uint32_t nn = (uint32_t)(B.off[i + 1] - B.off[i]);
-    if (i > 0 && !B.stock) HIP_OK(hipStreamWaitEvent(ks_, B.async ? B.done[i - 1] : lanes_[l - 1].done, 0));
+    const LaunchCtx C = batch_ctx(B, i, B.b);
+    const PathSet& L = *C.ps;
+    const hipStream_t s = C.stream;
+    const uint32_t nn = (uint32_t)C.paths;
+    if (i > 0 && !B.stock) HIP_OK(hipStreamWaitEvent(s, B.async ? B.done[i - 1] : lanes_[l - 1].done, 0));
     if (B.stock)
-      k_stock_store<<<blocks_for(nn), kBlock, 0, ks_>>>(p_pixel_, nn, p_col_, d_stock_);
+      k_stock_store<<<blocks_for(nn), kBlock, 0, s>>>(L.pixel, nn, L.col, d_stock_);
     else if (round)
-      LAUNCH_TIMED(4, accumulate, n_accumulate,
-                   k_accumulate_round<<<blocks_for(nn), kBlock, 0, ks_>>>(part, nn, p_pixel_, p_col_, d_acc_, d_cnt_));
+      LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
+                   k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, d_acc_, d_cnt_));
     else
-      LAUNCH_TIMED(4, accumulate, n_accumulate,
-                   k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, ks_>>>(
-                       part, B.k0 + B.off[i], nn, npix, p_col_, d_acc_, d_cnt_));
+      LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
+                   k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, s>>>(
+                       part, B.k0 + B.off[i], nn, npix, L.col, d_acc_, d_cnt_));
     HIP_OK(hipGetLastError());
     // ray statistics from the per-bounce counts (done: after this copy too)
-    uint32_t* hc = B.async ? B.hc + (size_t)i * kCountWords : h_counts_;
-    HIP_OK(hipMemcpyAsync(hc, d_counts_, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord),
-                          hipMemcpyDeviceToHost, ks_));
-    HIP_OK(hipEventRecord(B.async ? B.done[i] : lanes_[l].done, ks_));
+    uint32_t* hc = B.async ? B.hc + (size_t)i * kCountWords : L.h_counts;
+    HIP_OK(hipMemcpyAsync(hc, L.counts, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord),
+                          hipMemcpyDeviceToHost, s));
+    HIP_OK(hipEventRecord(B.async ? B.done[i] : L.done, s));
   }
-  bind_lane(0);
   if (!B.async) {
     for (int i = 1; i < B.nl; i++) HIP_OK(hipStreamWaitEvent(stream_, lanes_[B.lane0 + i].done, 0));
     pend_nl_ = B.nl;
@@ -3405,7 +3367,6 @@ bool Renderer::pump(bool block, std::string& err) {
       q.pop_front();
     }
   }
-  bind_lane(0);
   return true;
 }
 
@@ -3420,7 +3381,6 @@ bool Renderer::wait_issued(Batch* B, std::string& err) {
     if (!batch_advance(H, true, err)) return false;
     q.pop_front();
   }
-  bind_lane(0);
   return true;
 }
 
@@ -3435,13 +3395,35 @@ bool Renderer::drain_async(std::string& err) {
   return true;
 }
 
-// Lane l's buffers for batch B: on the lane's stream, or for an async batch
-// with WPT_OPT_ASYNC_PRIO on its low-priority stream.
-void Renderer::bind_batch_lane(const Batch& B, int l) {
-  bind_lane(l);
-  async_launch_ = B.async;
-  async_paths_ = B.off[l - B.lane0 + 1] - B.off[l - B.lane0];
-  if (B.async && async_prio_ && lanes_[l].lo) ks_ = lanes_[l].lo;
+// The launches of B's slice i at bounce b: on its lane's stream, or for an
+// async batch with WPT_OPT_ASYNC_PRIO on the lane's low-priority stream.
+// (Batches that presolve nothing keep one pair of hit-record buffers.)
+LaunchCtx Renderer::batch_ctx(const Batch& B, int i, int b) const {
+  LaunchCtx C;
+  C.lane = B.lane0 + i;
+  C.ps = &lanes_[C.lane];
+  C.stream = B.async && async_prio_ && C.ps->lo ? C.ps->lo : C.ps->stream;
+  C.async = B.async;
+  C.paths = B.off[i + 1] - B.off[i];
+  C.batch_lanes = B.nl;
+  C.timed = profiling_ && !B.async;
+  C.count = counting_;
+  C.bounce = b;
+  if (B.presolve) {
+    C.hit_sel = b & 1;
+    C.probe_res = reinterpret_cast<const uint32_t*>(C.ps->res_ctr(b));
+  }
+  return C;
+}
+
+// Lane 0 alone (the test hooks, the photon build): its stream, full-capacity
+// traversal grids, never timed.
+LaunchCtx Renderer::lane0_ctx(bool count) const {
+  LaunchCtx C;
+  C.ps = &lanes_[0];
+  C.stream = lanes_[0].stream;
+  C.count = count;
+  return C;
 }
 
 // ---------------------------------------------------------------------------
@@ -3899,7 +3881,6 @@ bool Renderer::run_batch(uint64_t k0, uint64_t n, int half, std::string& err, co
   if (!batch_begin(B, err)) return false;
   while (B.state != Batch::kIssued)
     if (!batch_advance(B, true, err)) return false;
-  time_launches_ = false;
   if (profiling_) {
     for (int i = 0; i < B.nl; i++) HIP_OK(hipStreamSynchronize(lanes_[i].stream));
     if (!resolve_timings(err)) return false;
@@ -4132,90 +4113,92 @@ bool Renderer::copy_partition(float* dev_dst, std::string& err) {
 
 // Launch one bounce of the extend kernel over rays (ro, rd) 0..*cnt-1 with
 // the scene's traversal (trav_ext_: 0 exact BVH2, 1 BVH4 fast path). Hits go
-// to the bound lane's t / id.
-bool Renderer::launch_extend(const float4* ro, const float4* rd, const uint32_t* cnt, std::string& err) {
-  const int v = (ds_.tri_only ? 1 : 0) | (counting_ ? 2 : 0) | (trav_ext_ << 2);
-  const int full = batch_lanes_ == 1 ? kTravVariants : 0;
-  const uint32_t g = std::min(async_grid(grid_ext_[v + full], 100), spill_grid());
-  ds_.probe = probe_slot(1, g);
-#define WPT_EXT(T, C, F) \
-  k_extend<T, C, F><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, cnt, hit_t(hit_sel_), hit_id(hit_sel_), d_spill_, d_work_, \
-                                            d_fallback_)
+// to the hit records C.hit_sel of C's lane.
+bool Renderer::launch_extend(const LaunchCtx& C, const float4* ro, const float4* rd, const uint32_t* cnt,
+                             std::string& err) {
+  const PathSet& L = *C.ps;
+  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0) | (trav_ext_ << 2);
+  const int full = C.batch_lanes == 1 ? kTravVariants : 0;
+  const uint32_t g = std::min(async_grid(C, grid_ext_[v + full], 100), spill_grid(L));
+  DevScene ds = ds_;
+  ds.probe = probe_slot(C, 1, g);
+#define WPT_EXT(T, CN, F)                                                                                     \
+  k_extend<T, CN, F><<<g, kTBlock, 0, C.stream>>>(ds, ro, rd, cnt, L.hit_t(C.hit_sel), L.hit_id(C.hit_sel), \
+                                                 L.spill, d_work_, d_fallback_)
   switch (v) {
-    case 0: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(false, false, 0)); break;
-    case 1: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, false, 0)); break;
-    case 2: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(false, true, 0)); break;
-    case 3: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, true, 0)); break;
-    case 4: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(false, false, 1)); break;
-    case 5: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, false, 1)); break;
-    case 6: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(false, true, 1)); break;
-    default: LAUNCH_TIMED(1, extend, n_extend, WPT_EXT(true, true, 1)); break;
+    case 0: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, false, 0)); break;
+    case 1: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, false, 0)); break;
+    case 2: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, true, 0)); break;
+    case 3: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, true, 0)); break;
+    case 4: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, false, 1)); break;
+    case 5: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, false, 1)); break;
+    case 6: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, true, 1)); break;
+    default: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, true, 1)); break;
   }
 #undef WPT_EXT
-  if (ds_.probe && probe_res_) {
-    k_probe_add<<<1, 1, 0, ks_>>>(ds_.probe, probe_res_);
+  if (ds.probe && C.probe_res) {
+    k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
     HIP_OK(hipGetLastError());
   }
-  ds_.probe = nullptr;
   return true;
 }
 
-// The bound lane's shadow stream, rays 0..*cnt-1 (trav_sh_ as launch_extend).
-bool Renderer::launch_shadow(const uint32_t* cnt, uint8_t* occ_out, std::string& err) {
-  const int v = (ds_.tri_only ? 1 : 0) | (counting_ ? 2 : 0) | (trav_sh_ << 2);
-  const int full = batch_lanes_ == 1 ? kTravVariants : 0;
-  const uint32_t g = std::min(async_grid(grid_sh_[v + full], 100), spill_grid());
-  ds_.probe = probe_slot(3, g);
-#define WPT_SH(T, C, F)                                                                                        \
-  k_shadow<T, C, F><<<g, kTBlock, 0, ks_>>>(ds_, cnt, s_o_, s_d_, s_c_, p_col_, occ_out, d_spill_, d_work_, \
-                                           d_fallback_)
+// The shadow stream of C's lane, rays 0..*cnt-1 (trav_sh_ as launch_extend).
+bool Renderer::launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* occ_out, std::string& err) {
+  const PathSet& L = *C.ps;
+  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0) | (trav_sh_ << 2);
+  const int full = C.batch_lanes == 1 ? kTravVariants : 0;
+  const uint32_t g = std::min(async_grid(C, grid_sh_[v + full], 100), spill_grid(L));
+  DevScene ds = ds_;
+  ds.probe = probe_slot(C, 3, g);
+#define WPT_SH(T, CN, F)                                                                                        \
+  k_shadow<T, CN, F><<<g, kTBlock, 0, C.stream>>>(ds, cnt, L.so, L.sd, L.sc, L.col, occ_out, L.spill, d_work_, \
+                                                 d_fallback_)
   switch (v) {
-    case 0: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(false, false, 0)); break;
-    case 1: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(true, false, 0)); break;
-    case 2: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(false, true, 0)); break;
-    case 3: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(true, true, 0)); break;
-    case 4: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(false, false, 1)); break;
-    case 5: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(true, false, 1)); break;
-    case 6: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(false, true, 1)); break;
-    default: LAUNCH_TIMED(3, shadow, n_shadow, WPT_SH(true, true, 1)); break;
+    case 0: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, false, 0)); break;
+    case 1: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, false, 0)); break;
+    case 2: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, true, 0)); break;
+    case 3: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, true, 0)); break;
+    case 4: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, false, 1)); break;
+    case 5: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, false, 1)); break;
+    case 6: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, true, 1)); break;
+    default: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, true, 1)); break;
   }
 #undef WPT_SH
-  ds_.probe = nullptr;
   return true;
 }
 
-// Bounce b's extension rays and bounce b-1's shadow rays of the bound lane
-// in one launch (exact BVH2; the fused form never runs the BVH4 fast path).
-bool Renderer::launch_trace(int b, std::string& err) {
-  const int v = (ds_.tri_only ? 1 : 0) | (counting_ ? 2 : 0);
-  const uint32_t g = std::min(async_grid(grid_tr_[v], trace_grid_pct_, 2), spill_grid());  // extension + shadow rays
-  const float4* ro = p_ro_[b & 1];
-  const float4* rd = p_rd_[b & 1];
-  const uint32_t* ce = ext_count(b);
-  const uint32_t* cs = sh_count(b - 1);
-  ds_.probe = probe_slot(5, g);
-#define WPT_TR(T, C) \
-  k_trace<T, C><<<g, kTBlock, 0, ks_>>>(ds_, ro, rd, ce, hit_t(hit_sel_), hit_id(hit_sel_), cs, s_o_, s_d_, s_c_, \
-                                        p_col_, d_spill_, d_work_)
+// Bounce b = C.bounce's extension rays and bounce b-1's shadow rays of C's
+// lane in one launch (exact BVH2; the fused form never runs the BVH4 fast path).
+bool Renderer::launch_trace(const LaunchCtx& C, std::string& err) {
+  const PathSet& L = *C.ps;
+  const int b = C.bounce;
+  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0);
+  // extension + shadow rays
+  const uint32_t g = std::min(async_grid(C, grid_tr_[v], trace_grid_pct_, 2), spill_grid(L));
+  DevScene ds = ds_;
+  ds.probe = probe_slot(C, 5, g);
+#define WPT_TR(T, CN)                                                                                          \
+  k_trace<T, CN><<<g, kTBlock, 0, C.stream>>>(ds, L.ro[b & 1], L.rd[b & 1], L.ext_count(b), L.hit_t(C.hit_sel), \
+                                             L.hit_id(C.hit_sel), L.sh_count(b - 1), L.so, L.sd, L.sc, L.col,  \
+                                             L.spill, d_work_)
   switch (v) {
-    case 0: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(false, false)); break;
-    case 1: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(true, false)); break;
-    case 2: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(false, true)); break;
-    default: LAUNCH_TIMED(5, trace, n_trace, WPT_TR(true, true)); break;
+    case 0: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(false, false)); break;
+    case 1: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(true, false)); break;
+    case 2: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(false, true)); break;
+    default: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(true, true)); break;
   }
 #undef WPT_TR
-  if (ds_.probe && probe_res_) {
-    k_probe_add<<<1, 1, 0, ks_>>>(ds_.probe, probe_res_);
-    if (hipGetLastError() != hipSuccess) { err = "k_probe_add launch failed"; ds_.probe = nullptr; return false; }
+  if (ds.probe && C.probe_res) {
+    k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
+    HIP_OK(hipGetLastError());
   }
-  ds_.probe = nullptr;
-  (void)err;
   return true;
 }
 
-// The wave-timeline record of the next traversal launch (kernel 1 extend, 3
+// The wave-timeline record of C's traversal launch (kernel 1 extend, 3
 // shadow, 5 trace) of `grid` blocks, or null when probing is off or full.
-uint4* Renderer::probe_slot(int kernel, uint32_t grid) {
+uint4* Renderer::probe_slot(const LaunchCtx& C, int kernel, uint32_t grid) {
   if (probe_used_ >= probe_cap_) return nullptr;
   const uint32_t waves = grid * (kTBlock / 64);
   if (!d_probe_) {
@@ -4232,7 +4215,7 @@ uint4* Renderer::probe_slot(int kernel, uint32_t grid) {
   }
   if (waves > probe_waves_) return nullptr;
   const uint32_t first = probe_used_ * probe_waves_;
-  probe_meta_.insert(probe_meta_.end(), {(uint32_t)kernel, (uint32_t)bound_, (uint32_t)cur_bounce_, waves, first});
+  probe_meta_.insert(probe_meta_.end(), {(uint32_t)kernel, (uint32_t)C.lane, (uint32_t)C.bounce, waves, first});
   probe_used_++;
   return d_probe_ + first;
 }
@@ -4257,11 +4240,11 @@ size_t Renderer::spill_slots() const {
   return (size_t)ds_.stack_cap > (size_t)kLdsSlots ? (size_t)ds_.stack_cap - kLdsSlots : 1;
 }
 
-// The most blocks a traversal launch on the bound lane may have: what its
-// spill area holds. Every launch is clamped to it (a smaller persistent grid
-// loops over more feed chunks, the same bits).
-uint32_t Renderer::spill_grid() const {
-  return (uint32_t)std::min<size_t>(spill_cap_ / (spill_slots() * kTBlock), 0xFFFFFFFFu);
+// The most blocks a traversal launch on lane L may have: what its spill area
+// holds. Every launch is clamped to it (a smaller persistent grid loops over
+// more feed chunks, the same bits).
+uint32_t Renderer::spill_grid(const PathSet& L) const {
+  return (uint32_t)std::min<size_t>(L.spill_cap / (spill_slots() * kTBlock), 0xFFFFFFFFu);
 }
 
 // Lane l's spill area for grids of `grid` blocks (one-shot async grids).
@@ -4276,7 +4259,6 @@ bool Renderer::ensure_spill(int l, uint32_t grid, std::string& err) {
   L.spill_cap = 0;
   HIP_OK(hipMalloc(&L.spill, need * sizeof(uint2)));
   L.spill_cap = need;
-  bind_lane(bound_);
   return true;
 }
 
@@ -4362,7 +4344,6 @@ bool Renderer::size_grids(std::string& err) {
       L.spill_cap = need;
     }
   }
-  bind_lane(bound_);
   return true;
 }
 
@@ -4693,7 +4674,6 @@ void Renderer::free_photons() {
 // reach a diffuse surface stops after 64 x kPhotonsNeeded shots with the
 // photons it has (the reference would keep shooting, tracing no paths).
 bool Renderer::build_photons(std::string& err) {
-  batch_lanes_ = 1;  // lane 0 alone: full-capacity traversal grids
   if (photons_ok_) return true;
   free_photons();
   PhotonTree tree(ds_.num_lights);
@@ -4703,25 +4683,23 @@ bool Renderer::build_photons(std::string& err) {
     if (!ensure_paths(R, err)) return false;
     std::vector<float4> hit(R);
     std::vector<uint32_t> lid(R);
-    const bool prof = profiling_, cnt = counting_;
-    profiling_ = counting_ = false;
+    const LaunchCtx C = lane0_ctx(false);  // its traversal is neither timed nor counted
+    const PathSet& L = lanes_[0];
     const uint64_t max_shots = 64ull * kPhotonsNeeded;
-    bool ok = true;
-    while (ok && tree.num_photons() < kPhotonsNeeded && photons_shot_ < max_shots) {
+    while (tree.num_photons() < kPhotonsNeeded && photons_shot_ < max_shots) {
       const uint32_t k0 = (uint32_t)photons_shot_;
-      k_photon_gen<<<blocks_for(R), kBlock, 0, stream_>>>(ds_, seed_, k0, R, p_ro_[0], p_rd_[0], p_thr_[0]);
+      k_photon_gen<<<blocks_for(R), kBlock, 0, stream_>>>(ds_, seed_, k0, R, L.ro[0], L.rd[0], L.thr[0]);
       HIP_OK(hipGetLastError());
-      h_counts_[0] = R;
-      HIP_OK(hipMemcpyAsync(d_counts_, h_counts_, 4, hipMemcpyHostToDevice, stream_));
-      ok = launch_extend(p_ro_[0], p_rd_[0], d_counts_, err);
-      if (!ok) break;
+      L.h_counts[0] = R;
+      HIP_OK(hipMemcpyAsync(L.counts, L.h_counts, 4, hipMemcpyHostToDevice, stream_));
+      if (!launch_extend(C, L.ro[0], L.rd[0], L.counts, err)) return false;
       if (ds_.tri_only)
-        k_photon_hit<true><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, p_ro_[0], p_rd_[0], p_t_, p_id_, p_thr_[0], p_col_, p_pixel_);
+        k_photon_hit<true><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, L.ro[0], L.rd[0], L.t, L.id, L.thr[0], L.col, L.pixel);
       else
-        k_photon_hit<false><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, p_ro_[0], p_rd_[0], p_t_, p_id_, p_thr_[0], p_col_, p_pixel_);
+        k_photon_hit<false><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, L.ro[0], L.rd[0], L.t, L.id, L.thr[0], L.col, L.pixel);
       HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpyAsync(hit.data(), p_col_, sizeof(float4) * R, hipMemcpyDeviceToHost, stream_));
-      HIP_OK(hipMemcpyAsync(lid.data(), p_pixel_, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream_));
+      HIP_OK(hipMemcpyAsync(hit.data(), L.col, sizeof(float4) * R, hipMemcpyDeviceToHost, stream_));
+      HIP_OK(hipMemcpyAsync(lid.data(), L.pixel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream_));
       HIP_OK(hipStreamSynchronize(stream_));
       uint32_t used = R;
       for (uint32_t i = 0; i < R; i++) {
@@ -4732,9 +4710,6 @@ bool Renderer::build_photons(std::string& err) {
       }
       photons_shot_ += used;
     }
-    profiling_ = prof;
-    counting_ = cnt;
-    if (!ok) return false;
   }
   photons_stored_ = tree.num_photons();
   stats_.photon_rays += photons_shot_;
@@ -4821,11 +4796,11 @@ bool Renderer::photon_tree(std::vector<uint32_t>& child, std::vector<float>& cum
 }
 
 bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err) {
-  batch_lanes_ = 1;  // lane 0 alone: full-capacity traversal grids
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   if (n > 0xFFFFFFFFull) { err = "too many rays"; return false; }
   if (!ensure_paths(n, err)) return false;
+  const PathSet& L = lanes_[0];
   std::vector<float4> o(n), d(n);
   for (size_t i = 0; i < n; i++) {
     const float* r = rays + 6 * i;
@@ -4833,16 +4808,12 @@ bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id
     d[i] = make_float4(r[3], r[4], r[5], 0.0f);
   }
   const uint32_t nn = (uint32_t)n;
-  HIP_OK(hipMemcpyAsync(p_ro_[0], o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(p_rd_[0], d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_counts_, &nn, 4, hipMemcpyHostToDevice, stream_));
-  const bool prof = profiling_;
-  profiling_ = false;
-  const bool ok = launch_extend(p_ro_[0], p_rd_[0], d_counts_, err);
-  profiling_ = prof;
-  if (!ok) return false;
-  HIP_OK(hipMemcpyAsync(t_out, p_t_, 4 * n, hipMemcpyDeviceToHost, stream_));
-  HIP_OK(hipMemcpyAsync(id_out, p_id_, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(L.ro[0], o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(L.rd[0], d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(L.counts, &nn, 4, hipMemcpyHostToDevice, stream_));
+  if (!launch_extend(lane0_ctx(counting_), L.ro[0], L.rd[0], L.counts, err)) return false;
+  HIP_OK(hipMemcpyAsync(t_out, L.t, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(id_out, L.id, 4 * n, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   return true;
 }
@@ -4878,7 +4849,6 @@ bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, flo
 // Parity hook: the production shadow kernel on caller-given (p, q, light);
 // the shadow ray is formed as Scene::shadow_ray does (scene.rs:105-108).
 bool Renderer::shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occ, std::string& err) {
-  batch_lanes_ = 1;  // lane 0 alone: full-capacity traversal grids
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   if (n > 0xFFFFFFFFull) { err = "too many rays"; return false; }
@@ -4899,13 +4869,11 @@ bool Renderer::shadow_rays(size_t n, const float* pq, const int32_t* light, uint
   uint8_t* dq = nullptr;
   HIP_OK(hipMalloc(&dq, n));
   const uint32_t nn = (uint32_t)n;
-  HIP_OK(hipMemcpyAsync(s_o_, o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(s_d_, d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_counts_, &nn, 4, hipMemcpyHostToDevice, stream_));
-  const bool prof = profiling_;
-  profiling_ = false;
-  const bool ok = launch_shadow(d_counts_, dq, err);
-  profiling_ = prof;
+  const PathSet& L = lanes_[0];
+  HIP_OK(hipMemcpyAsync(L.so, o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(L.sd, d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(L.counts, &nn, 4, hipMemcpyHostToDevice, stream_));
+  const bool ok = launch_shadow(lane0_ctx(counting_), L.counts, dq, err);
   if (ok) {
     HIP_OK(hipMemcpyAsync(occ, dq, n, hipMemcpyDeviceToHost, stream_));
     HIP_OK(hipStreamSynchronize(stream_));
