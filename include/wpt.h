@@ -271,7 +271,9 @@ int wpt_seq_sum_device(const float* v, uint64_t n, float* out);
  * out[40] = of rays, those their producer resolved (WPT_OPT_PRESOLVE: plane
  * or miss, never fed to a traversal kernel; a stock refill's count when traced),
  * out[41] = of out[40], the rays resolved to a miss that adds nothing to their
- * path and so never written to a ray stream (WPT_OPT_DROP_MISS).
+ * path and so never written to a ray stream (WPT_OPT_DROP_MISS),
+ * out[42] = of shadow rays, those their producer resolved as unoccluded and
+ * added itself, never fed to a traversal kernel (WPT_OPT_PRESOLVE_SHADOW).
  * Visit/test/byte/iteration counts are only gathered with counting on. */
 int wpt_stats(uint64_t* out, size_t n);
 /* per-kernel device time (profiling on): out[0..11] = {ms, launches} ×
@@ -342,6 +344,10 @@ int wpt_set_lanes(int32_t n);
 #define WPT_OPT_DROP_MISS 38     /* 1 (default): a ray its producer resolves to a miss (WPT_OPT_PRESOLVE) whose throughput *
                                     background is +0 in every component, the product the next shade would add, is counted
                                     and written to no stream; 0: it is appended and shaded like any resolved ray */
+#define WPT_OPT_PRESOLVE_SHADOW 39 /* 1 (default): k_shade's presolving variants add the NEE contribution of a shadow ray that
+                                    provably ends unoccluded (no plane before the light, every guard box missed or behind
+                                    it, no other light-guard triangle hit) and write it to no stream; 0: every shadow ray
+                                    is traversed. Effective only where WPT_OPT_PRESOLVE is; the frame is the same bits. */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -382,6 +388,10 @@ int wpt_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* oc
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */
 int wpt_presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out);
+/* Test hook: k_shade's presolve of shadow rays (WPT_OPT_PRESOLVE_SHADOW) on
+ * the device for n pairs {p.xyz, q.xyz} and light shape ids, the ray formed
+ * as by wpt_shadow_rays: resolved[i] = 1 if ray i provably ends unoccluded. */
+int wpt_presolve_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* resolved);
 
 /* Tear the session down (the reference never does); allows a new wpt_init.
  * The sample stock's two ring blocks (about 42 GB at 1080p) stay with the
@@ -409,6 +419,12 @@ int wpt_debug_scene_presolve(void* h, size_t n, const float* rays, uint8_t* reso
  * root's bounds, then 4 guards (x_min,y_min,z_min,x_max,y_max,z_max);
  * leaf_guard (may be NULL) = per BVH2 node the guard of a leaf, ~0 otherwise. */
 int wpt_debug_scene_guards(void* h, uint32_t* num_guards, float* boxes, uint32_t* leaf_guard);
+/* The shadow presolve's host restatement (as wpt_presolve_shadow_rays). */
+int wpt_debug_scene_presolve_shadow(void* h, size_t n, const float* pq, const int32_t* light, uint8_t* resolved);
+/* Its light guards: *light_guards = bit g set if guard g holds emissive
+ * triangles only; *num = their primitives together (0..4); ids (may be NULL)
+ * = 4 shape ids, -1 beyond *num. */
+int wpt_debug_scene_guard_lights(void* h, uint32_t* light_guards, uint32_t* num, int32_t* ids);
 void wpt_debug_scene_free(void* h);
 /* The same scene with its BVH2 built on the GPU (the device of
  * wpt_set_device, default 0) whatever its size; same accessors. */

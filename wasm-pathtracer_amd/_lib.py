@@ -61,6 +61,9 @@ _SIGS = {
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),
+    "wpt_presolve_shadow_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
+    "wpt_debug_scene_presolve_shadow": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p]),
+    "wpt_debug_scene_guard_lights": (ctypes.c_int, [c_p, c_p, c_p, c_p]),
     "wpt_shutdown": (ctypes.c_int, []),
     "wpt_debug_scene_new": (c_p, [c_i32, c_p, c_sz]),
     "wpt_debug_scene_info": (ctypes.c_int, [c_p, c_p]),

@@ -553,7 +553,7 @@ int wpt_stats(uint64_t* out, size_t n) {
   std::string err;
   if (!g_session->renderer.flush_counts(err)) return fail(WPT_ERR_DEVICE, err);
   const Stats& st = g_session->renderer.stats();
-  uint64_t v[42] = {st.paths,          st.rays,           st.shadow_rays,    st.node_visits,  st.prim_tests,
+  uint64_t v[43] = {st.paths,          st.rays,           st.shadow_rays,    st.node_visits,  st.prim_tests,
                     st.bounces,        st.ext_visits,     st.ext_tests,      st.ext_node_bytes, st.sh_visits,
                     st.sh_tests,       st.sh_node_bytes,  st.fallback_ext,   st.fallback_sh,  st.ext_lane_iters,
                     st.ext_live_iters, st.sh_lane_iters,  st.sh_live_iters,  st.photon_rays,  st.photons,
@@ -562,8 +562,8 @@ int wpt_stats(uint64_t* out, size_t n) {
                     st.ex_body_lanes,  st.ex_bodies,      st.lf_body_lanes,  st.lf_bodies,    st.stock_traced,
                     st.stock_deficit,  st.stock_waits,    st.plan_us,        st.stock_us,
                     st.stock_rays,     st.stock_rays_used, st.presolved_rays,
-                    st.dropped_rays};
-  for (size_t i = 0; i < n && i < 42; i++) out[i] = v[i];
+                    st.dropped_rays,   st.shadow_presolved_rays};
+  for (size_t i = 0; i < n && i < 43; i++) out[i] = v[i];
   return WPT_OK;
 }
 
@@ -736,6 +736,14 @@ int wpt_presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_o
   return WPT_OK;
 }
 
+int wpt_presolve_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* resolved) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (n && (!pq || !light || !resolved)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  std::string err;
+  if (!g_session->renderer.presolve_shadow_rays(n, pq, light, resolved, err)) return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 int wpt_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occluded) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   std::string err;
@@ -893,6 +901,50 @@ int wpt_debug_scene_presolve(void* h, size_t n, const float* rays, uint8_t* reso
     const float* r = rays + 6 * i;
     resolved[i] = presolve_ray(hp, pre, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), t_out[i], id_out[i]) ? 1 : 0;
   }
+  return WPT_OK;
+}
+
+// The host's planes and presolve data of a scene, as upload_scene lays them
+// out (planes: normal, normal . location).
+static void host_presolve_view(const HostScene* sc, HostPlanes& hp, PresolveBoxes& pre) {
+  hp = HostPlanes{};
+  pre = PresolveBoxes{};
+  if (sc->use_bvh && sc->shapes.size() > sc->num_inf && sc->num_inf <= 16) {
+    pre = sc->pre;
+    hp.num_inf = sc->num_inf;
+    for (uint32_t i = 0; i < sc->num_inf; i++) {
+      const float* g = sc->shapes[i].g;
+      const V3 loc = mk(g[0], g[1], g[2]), nrm = mk(g[3], g[4], g[5]);
+      hp.planes[i] = HostPlanes::P4{nrm.x, nrm.y, nrm.z, dot(nrm, loc)};
+    }
+  }
+}
+
+int wpt_debug_scene_presolve_shadow(void* h, size_t n, const float* pq, const int32_t* light, uint8_t* resolved) {
+  const HostScene* sc = (const HostScene*)h;
+  if (!sc || (n && (!pq || !light || !resolved))) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  // the host restatement: the same presolve_shadow on the operands
+  // shade_path derives from {p, q} (shadow_operands)
+  HostPlanes hp;
+  PresolveBoxes pre;
+  host_presolve_view(sc, hp, pre);
+  for (size_t i = 0; i < n; i++) {
+    const float* r = pq + 6 * i;
+    V3 o, d;
+    float dl;
+    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), o, d, dl);
+    resolved[i] = presolve_shadow(hp, pre, o, d, dl, light[i]) ? 1 : 0;
+  }
+  return WPT_OK;
+}
+
+int wpt_debug_scene_guard_lights(void* h, uint32_t* light_guards, uint32_t* num, int32_t* ids) {
+  const HostScene* sc = (const HostScene*)h;
+  if (!sc || !light_guards || !num) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  *light_guards = sc->pre.light_guards;
+  *num = sc->pre.num_guard_lights;
+  if (ids)
+    for (int k = 0; k < kMaxGuardLights; k++) ids[k] = (uint32_t)k < sc->pre.num_guard_lights ? sc->pre.guard_light_id[k] : -1;
   return WPT_OK;
 }
 

@@ -100,6 +100,7 @@ struct Stats {
   uint64_t stock_rays_used = 0;  // of rays + shadow_rays: those of samples taken from the stock
   uint64_t presolved_rays = 0;   // of rays: resolved by their producer (wpt_presolve.h), never fed to k_extend / k_trace
   uint64_t dropped_rays = 0;     // of presolved_rays: resolved to a miss that adds nothing, never written to a stream (WPT_OPT_DROP_MISS)
+  uint64_t shadow_presolved_rays = 0;  // of shadow_rays: resolved unoccluded by k_shade, never fed to k_shadow / k_trace (WPT_OPT_PRESOLVE_SHADOW)
 };
 
 // Kernel-time accumulators (ms), filled when profiling is on.
@@ -147,8 +148,15 @@ constexpr uint64_t kMinLanePaths = 1024;  // smaller batches run on one lane
 // path-at-a-time tail of RR-only batches)
 constexpr size_t kFinishWord = 2 + 2 * (size_t)kMaxBounces;
 constexpr size_t kResWord = kFinishWord + 4;     // k_finish: rays, shadow rays, paths, longest path (bounces)
-constexpr size_t kCountWords = kResWord + 2 * ((size_t)kMaxBounces + 1);
-static_assert(kResWord % 2 == 0, "the presolved counts are 64-bit slots");
+// after the presolved counts: per bounce b a 64-bit slot at u32 index
+// kShResWord + 2b whose low word counts the shadow rays of bounce b that
+// k_shade resolved itself (presolve_shadow, WPT_OPT_PRESOLVE_SHADOW): they are
+// in no stream, so the device never reads it; the host adds it to the bounce's
+// shadow rays. (k_shade reaches it from the append counter: kShResWord - 2
+// words past append_ctr(b).)
+constexpr size_t kShResWord = kResWord + 2 * ((size_t)kMaxBounces + 1);
+constexpr size_t kCountWords = kShResWord + 2 * ((size_t)kMaxBounces + 1);
+static_assert(kResWord % 2 == 0 && kShResWord % 2 == 0, "the presolved counts are 64-bit slots");
 constexpr uint32_t kWorkWords = 16;   // device work counters (COUNT builds), see d_work_
 constexpr uint32_t kWorkCopies = 64;  // copies of them, one per blockIdx % 64 (spreads the atomics)
 struct PathSet {
@@ -294,6 +302,8 @@ class Renderer {
   bool trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err);
   // test hook: presolve_ray on the device over caller-given rays
   bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
+  // test hook: presolve_shadow on the device over caller-given {p, q} pairs
+  bool presolve_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* resolved, std::string& err);
   bool shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occ, std::string& err);
   // the recorded wave timelines (WPT_OPT_PROBE), then recording restarts
   bool probe_read(std::vector<uint32_t>& meta, std::vector<uint4>& rec, double& ticks_per_us, std::string& err);
@@ -563,8 +573,10 @@ class Renderer {
   uint64_t finish_below_ = 1u << 18;  // WPT_OPT_FINISH_BELOW: RR-only batches hand their last paths to k_finish (0: never)
   int finish_every_ = 4;           // WPT_OPT_FINISH_EVERY: bounces between the RR-only batches' live-count reads
   uint32_t num_guards_ = 0;        // the uploaded scene's guard boxes (0: its rays are never presolved)
+  uint32_t light_guards_ = 0;      // its light guards (bit mask; 0: k_shade does not try to resolve shadow rays)
   bool presolve_ = true;           // WPT_OPT_PRESOLVE: producers resolve plane-or-miss extension rays (wpt_presolve.h)
   bool drop_miss_ = true;          // WPT_OPT_DROP_MISS: a ray resolved to a miss that adds nothing is not written to the next stream
+  bool presolve_shadow_ = true;    // WPT_OPT_PRESOLVE_SHADOW: k_shade adds the contribution of a shadow ray it resolves unoccluded
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
   uint32_t probe_cap_ = 0, probe_waves_ = 0, probe_used_ = 0;

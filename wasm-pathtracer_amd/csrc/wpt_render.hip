@@ -1278,6 +1278,7 @@ struct ShadeParams {
   int max_depth;
   int debug;
   int drop_miss;  // WPT_OPT_DROP_MISS (k_shade's presolving variants)
+  int presolve_shadow;  // WPT_OPT_PRESOLVE_SHADOW (the same variants)
 };
 
 // Dense per-bounce streams of the wavefront. The live paths of bounce b are
@@ -1458,6 +1459,18 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
   if (!R.alive) end_counts((flags >> kShadowShift) + (R.shadow ? 1u : 0u));
 }
 
+// NEE contribution of a shadow ray k_shade resolved itself: col[path] += c.xyz,
+// add_contribution's sums (below). It leaves col[path].w alone: with CR a path
+// that ends has just stored its ray counts there as a u32, a store the
+// compiler may not order against a float4 load of the same bytes.
+__device__ __forceinline__ void add_contribution_xyz(float4* __restrict__ col, float4 c) {
+  float* p = &col[__float_as_uint(c.w)].x;
+  const float x = p[0] + c.x, y = p[1] + c.y, z = p[2] + c.z;
+  p[0] = x;
+  p[1] = y;
+  p[2] = z;
+}
+
 // Shade kernel: one bounce of the path loop for paths 0..n-1 of the input
 // stream. A block shades kShadeBlock (256) consecutive paths, then appends the survivors
 // and the shadow rays in path order: one block-wide scan of the two flags and
@@ -1481,9 +1494,14 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
 // +0 in every component: that is the product, on the same operands, the next
 // shade_path would test before it returns, so nothing reads the record. A
 // dropped ray goes to neither end of the next stream and is counted in the
-// high word of the presolved slot (the scan carries resolved | dropped << 16
-// per wave, at most 64 each, so the same column and the same atomic serve);
+// high word of the presolved slot (the scan carries three 10-bit fields per
+// wave, resolved | dropped << 10 | resolved shadow rays << 20, at most 256 each
+// over the block, so the same column and the same atomic serve);
 // with CR it writes the count word the next bounce's end_counts would have.
+// A shadow ray that presolve_shadow resolves (P.presolve_shadow) is added to
+// col here and written to no stream; it is counted in the bounce's slot at
+// kShResWord by a third lane of the same atomic. The append counter's high
+// word, which k_shadow / k_trace read, counts the streamed shadow rays only.
 // OCT (PNEE): where photon_sample reads the octree: 0 global memory, 1 the
 // child array from LDS, 2 child array and CDFs from LDS (oct_lds_words).
 template <bool TRI_ONLY, bool PNEE, int OCT, bool CR = false, bool PS = false>
@@ -1495,7 +1513,8 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
                                                        float* __restrict__ t_nx, int32_t* __restrict__ id_nx,
                                                        uint32_t end) {
   constexpr uint32_t kWaves = kShadeBlock / 64;
-  static_assert(kWaves < 64, "the scan's totals and the second atomic lane sit in one wave");
+  static_assert(kWaves + 1 < 64, "the scan's totals and the other atomic lanes sit in one wave");
+  static_assert(kShadeBlock < 1024, "three 10-bit fields in the scan's third column");
   __shared__ uint32_t s_off[PS ? 3 : 2][kWaves];
   __shared__ f4v s_light[5 * kShadeLights];
   const uint32_t nh = *count;
@@ -1567,12 +1586,27 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
         }
       }
     }
-    const uint64_t am = __ballot(R.alive && !res), sm = __ballot(R.shadow), rm = PS ? __ballot(res) : 0ull;
-    const uint64_t dm = PS ? __ballot(drop) : 0ull;
+    // The shadow ray: one that provably ends unoccluded (presolve_shadow,
+    // wpt_presolve.h) adds its contribution in this launch, the
+    // read-modify-write k_shadow would do (below, where the other lanes store
+    // their shadow rays), and takes no slot of the shadow stream. The path's
+    // additions keep their order: shade_path adds nothing to col for a path
+    // that emits a shadow ray, and this launch runs after the traversal of
+    // the previous bounce's shadow rays. (After a CR path's count word.)
+    // (Not in the PNEE variant that reads the octree from global memory: with
+    // it that variant needs 24 B of scratch where it had 20.)
+    bool sres = false;
+    if constexpr (PS && !(PNEE && OCT == 0)) {
+      if (R.shadow && P.presolve_shadow)
+        sres = presolve_shadow(S, *S.pre, ld3(R.so), ld3(R.sd), R.so.w, (int32_t)__float_as_uint(R.sd.w));
+    }
+    const uint64_t am = __ballot(R.alive && !res), sm = __ballot(R.shadow && !sres), rm = PS ? __ballot(res) : 0ull;
+    const uint64_t dm = PS ? __ballot(drop) : 0ull, zm = PS ? __ballot(sres) : 0ull;
     if (lane == 0) {
       s_off[0][wid] = (uint32_t)__popcll(am);
       s_off[1][wid] = (uint32_t)__popcll(sm);
-      if constexpr (PS) s_off[2][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 16);
+      if constexpr (PS)
+        s_off[2][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 10) | ((uint32_t)__popcll(zm) << 20);
     }
     __syncthreads();
     if constexpr (!PS) {
@@ -1606,19 +1640,22 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
       unsigned long long base = 0ull;
       // the second counter's distance, made here: as a plain constant the
       // compiler keeps it in a VGPR across the whole loop (shade_path's peak)
+      // lane kWaves + 1: the shadow rays resolved here, into this bounce's
+      // slot of the block after the presolved counts (kShResWord)
       uint32_t off;
       asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)(kResWord / 2)));
-      if (lane == kWaves - 1 || lane == kWaves)
-        base = atomicAdd(append + (lane == kWaves - 1 ? 0u : off),
-                         lane == kWaves - 1 ? ((unsigned long long)ia | ((unsigned long long)ib << 32))
-                                            : ((unsigned long long)(tc & 0xffffu) | ((unsigned long long)(tc >> 16) << 32)));
+      if (lane == kWaves + 1) asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)((kShResWord - 2) / 2)));
+      unsigned long long inc = (unsigned long long)ia | ((unsigned long long)ib << 32);
+      if (lane == kWaves) inc = (unsigned long long)(tc & 0x3ffu) | ((unsigned long long)((tc >> 10) & 0x3ffu) << 32);
+      if (lane == kWaves + 1) inc = (unsigned long long)(tc >> 20);
+      if (lane >= kWaves - 1 && lane <= kWaves + 1) base = atomicAdd(append + (lane == kWaves - 1 ? 0u : off), inc);
       const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
       const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
       const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
       if (lane < kWaves) {
         s_off[0][lane] = ba + ia - a;
         s_off[1][lane] = bb + ib - b;
-        s_off[2][lane] = bc + ((ic - c) & 0xffffu);
+        s_off[2][lane] = bc + ((ic - c) & 0x3ffu);
       }
     }
     __syncthreads();
@@ -1637,7 +1674,9 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
         }
       }
     }
-    if (R.shadow) {
+    if (sres) {
+      add_contribution_xyz(col, R.sc);
+    } else if (R.shadow) {
       const uint32_t p = s_off[1][wid] + (uint32_t)__popcll(sm & below);
       st_stream(sh.o + p, R.so);
       st_stream(sh.d + p, R.sd);
@@ -2186,6 +2225,9 @@ __global__ void __launch_bounds__(kTBlock, TRI_ONLY ? WPT_FINISH_WAVES : 1) k_fi
 // presolved slot, the resolved rays at the back of the stream and the dropped
 // ones (WPT_OPT_DROP_MISS). Launched only while the probe records.
 __global__ void k_probe_add(uint4* rec, const uint32_t* __restrict__ res) { rec[0].w += res[0] + res[1]; }
+// The same for a launch that holds shadow rays: those k_shade resolved itself
+// (the low word of the bounce's slot at kShResWord).
+__global__ void k_probe_add_sh(uint4* rec, const uint32_t* __restrict__ sres) { rec[0].w += sres[0]; }
 
 // Test hook: presolve_ray (wpt_presolve.h) as the producers run it, over
 // caller-given rays (6 floats each: origin, direction).
@@ -2201,6 +2243,18 @@ __global__ void __launch_bounds__(kBlock) k_presolve(DevScene S, uint32_t n, con
   resolved[i] = res ? 1 : 0;
   t_out[i] = t;
   id_out[i] = id;
+}
+
+// Test hook: presolve_shadow (wpt_presolve.h) as k_shade runs it, over shadow
+// rays in the shadow stream's layout (so: origin, |q - p|; sd: direction,
+// light shape id).
+__global__ void __launch_bounds__(kBlock) k_presolve_shadow(DevScene S, uint32_t n, const float4* __restrict__ so,
+                                                            const float4* __restrict__ sd,
+                                                            uint8_t* __restrict__ resolved) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 o = so[i], d = sd[i];
+  resolved[i] = presolve_shadow(S, *S.pre, ld3(o), ld3(d), o.w, (int32_t)__float_as_uint(d.w)) ? 1 : 0;
 }
 
 // RenderTarget::write (render_target.rs:55-58): acc += v, count += 1, per
@@ -2477,14 +2531,7 @@ bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
     memset(out, 0, 4 * sizeof(float4));
     const float* g = s.g;
     if (s.kind == kTri) {
-      V3 v0 = mk(g[0], g[1], g[2]), v1 = mk(g[3], g[4], g[5]), v2 = mk(g[6], g[7], g[8]);
-      V3 n = cross(sub(v1, v0), sub(v2, v0));  // triangle.rs:164
-      V3 nn = normalize(n);                     // triangle.rs:183
-      float od = dot(n, v0);                    // triangle.rs:172
-      out[0] = make_float4(v0.x, v0.y, v0.z, n.x);
-      out[1] = make_float4(v1.x, v1.y, v1.z, n.y);
-      out[2] = make_float4(v2.x, v2.y, v2.z, n.z);
-      out[3] = make_float4(nn.x, nn.y, nn.z, od);
+      tri_record(g, &out[0].x);  // wpt_presolve.h: the light guards' records are the same bits
     } else if (s.kind == kPlane) {
       V3 loc = mk(g[0], g[1], g[2]), n = mk(g[3], g[4], g[5]);
       out[0] = make_float4(n.x, n.y, n.z, dot(n, loc));  // plane.rs:80-99
@@ -2642,6 +2689,7 @@ bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
     if (!up(&pre, sizeof pre, &p)) return false;
     ds.pre = (const PresolveBoxes*)p;
     num_guards_ = pre.num_guards;
+    light_guards_ = pre.light_guards;
   }
   ds_ = ds;
   depth_ = sc.depth;
@@ -2707,6 +2755,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 36: if (!range(0, (int64_t)1 << 40)) return false; async_fused_below_ = (uint64_t)v; return true;
     case 37: if (!range(0, 1)) return false; presolve_ = v != 0; return true;
     case 38: if (!range(0, 1)) return false; drop_miss_ = v != 0; return true;
+    case 39: if (!range(0, 1)) return false; presolve_shadow_ = v != 0; return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -2760,6 +2809,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 36: v = (int64_t)async_fused_below_; return true;
     case 37: v = presolve_ ? 1 : 0; return true;
     case 38: v = drop_miss_ ? 1 : 0; return true;
+    case 39: v = presolve_shadow_ ? 1 : 0; return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -3021,9 +3071,12 @@ static void add_counts(Stats& st, const uint32_t* hc, int b, bool stock, bool pr
     const uint32_t drop = presolve ? hc[kResWord + 2 * i + 1] : 0u;
     const uint64_t res = (uint64_t)(presolve ? hc[kResWord + 2 * i] : 0u) + drop;
     r += (i == 0 ? hc[0] : hc[2 + 2 * (i - 1)]) + res;
-    sr += hc[3 + 2 * i];
+    // the shadow rays k_shadow / k_trace saw plus those k_shade resolved
+    const uint32_t sres = presolve ? hc[kShResWord + 2 * i] : 0u;
+    sr += (uint64_t)hc[3 + 2 * i] + sres;
     st.presolved_rays += res;  // (a stock batch's too, when traced)
     st.dropped_rays += drop;
+    st.shadow_presolved_rays += sres;
   }
   r += hc[kFinishWord];
   sr += hc[kFinishWord + 1];
@@ -3122,7 +3175,10 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
 // of an RR-only batch must come back first. block: wait for such counts;
 // else return with B in kCountWait when they have not landed yet.
 bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
-  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0};
+  // Without a light guard the light lies inside an ordinary guard, whose box
+  // the ray's target is in: next to nothing resolves (the museum), so k_shade
+  // does not try.
+  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
   // the paths of C's lane in stream rin, to their end, one lane each
   auto launch_finish = [&](const LaunchCtx& C, const RayStream& rin, uint32_t g, bool pn) -> bool {
     const PathSet& L = *C.ps;
@@ -4165,6 +4221,11 @@ bool Renderer::launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* o
     default: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, true, 1)); break;
   }
 #undef WPT_SH
+  // (cnt is the bounce's sh_count: its resolved slot lies kShResWord - 3 words on)
+  if (ds.probe && C.probe_res) {
+    k_probe_add_sh<<<1, 1, 0, C.stream>>>(ds.probe, cnt + (kShResWord - 3));
+    HIP_OK(hipGetLastError());
+  }
   return true;
 }
 
@@ -4191,6 +4252,7 @@ bool Renderer::launch_trace(const LaunchCtx& C, std::string& err) {
 #undef WPT_TR
   if (ds.probe && C.probe_res) {
     k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
+    k_probe_add_sh<<<1, 1, 0, C.stream>>>(ds.probe, L.sh_count(b - 1) + (kShResWord - 3));
     HIP_OK(hipGetLastError());
   }
   return true;
@@ -4843,6 +4905,41 @@ bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, flo
   (void)hipFree(di);
   (void)hipFree(df);
   if (!ok) err = "HIP error in presolve_rays";
+  return ok;
+}
+
+bool Renderer::presolve_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* resolved,
+                                    std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (n == 0) return true;
+  if (n > 0xFFFFFFFFull / 16) { err = "too many rays"; return false; }
+  std::vector<float4> o(n), d(n);
+  for (size_t i = 0; i < n; i++) {
+    const float* r = pq + 6 * i;
+    V3 org, dir;
+    float dl;
+    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), org, dir, dl);
+    o[i] = make_float4(org.x, org.y, org.z, dl);
+    d[i] = make_float4(dir.x, dir.y, dir.z, u2f((uint32_t)light[i]));
+  }
+  float4* dso = nullptr;
+  float4* dsd = nullptr;
+  uint8_t* df = nullptr;
+  bool ok = hipMalloc(&dso, 16 * n) == hipSuccess && hipMalloc(&dsd, 16 * n) == hipSuccess &&
+            hipMalloc(&df, n) == hipSuccess;
+  if (ok)
+    ok = hipMemcpyAsync(dso, o.data(), 16 * n, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+         hipMemcpyAsync(dsd, d.data(), 16 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
+  if (ok) {
+    k_presolve_shadow<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dso, dsd, df);
+    ok = hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipStreamSynchronize(stream_) == hipSuccess;
+  }
+  (void)hipFree(dso);
+  (void)hipFree(dsd);
+  (void)hipFree(df);
+  if (!ok) err = "HIP error in presolve_shadow_rays";
   return ok;
 }
 

@@ -432,6 +432,27 @@ void build_guards(HostScene& sc) {
     for (int k = 0; k < 6; k++) sc.pre.guard[i][k] = groups[i].b[k];
     for (uint32_t n : groups[i].leaves) sc.leaf_guard[n] = (uint32_t)i;
   }
+  // Light guards (presolve_shadow): the groups whose leaves hold emissive
+  // triangles only, taken in order while their primitives together fit
+  // kMaxGuardLights; a group over that stays an ordinary guard.
+  for (size_t i = 0; i < groups.size(); i++) {
+    std::vector<uint32_t> prims;
+    bool lights_only = true;
+    for (uint32_t n : groups[i].leaves)
+      for (uint32_t k = 0; k < sc.nodes[n].count && lights_only; k++) {
+        const size_t sid = (size_t)sc.num_inf + sc.nodes[n].left_first + k;
+        lights_only = sid < sc.shapes.size() && sc.shapes[sid].kind == kTri && sc.shapes[sid].emissive &&
+                      prims.size() < (size_t)kMaxGuardLights;
+        prims.push_back((uint32_t)sid);
+      }
+    if (!lights_only || prims.empty() || sc.pre.num_guard_lights + prims.size() > (size_t)kMaxGuardLights) continue;
+    sc.pre.light_guards |= 1u << i;
+    for (uint32_t sid : prims) {
+      const uint32_t k = sc.pre.num_guard_lights++;
+      sc.pre.guard_light_id[k] = (int32_t)sid;
+      tri_record(sc.shapes[sid].g, sc.pre.guard_light[k]);
+    }
+  }
 }
 
 bool scene_init(HostScene& sc, std::vector<Shape> shapes, const float bg[3], Bvh2Builder* gpu, std::string* err) {

@@ -225,7 +225,8 @@ def stats():
             "sum_chunks", "sum_resummed", "sum_fetched", "stock_consumed", "fill_paths", "trace_bytes",
             "finish_paths", "finish_max_bounces", "max_ray_visits", "ex_body_lanes", "ex_bodies", "lf_body_lanes",
             "lf_bodies", "stock_traced", "stock_deficit", "stock_waits", "plan_us", "stock_us",
-            "stock_rays", "stock_rays_used", "presolved_rays", "dropped_rays")
+            "stock_rays", "stock_rays_used", "presolved_rays", "dropped_rays",
+            "shadow_presolved_rays")
     out = (ctypes.c_uint64 * len(keys))()
     _check(lib().wpt_stats(ctypes.addressof(out), len(keys)))
     return dict(zip(keys, list(out)))
@@ -270,7 +271,8 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "finish_below": 13, "trace_grid_pct": 14, "finish_every": 20, "probe": 22, "stock": 23, "stock_lanes": 24,
            "fill": 25, "async_prio": 26, "async_grid_pct": 27, "scene_traversal": 28, "scene_tri_only": 29,
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
-           "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38}
+           "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
+           "presolve_shadow": 39}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -354,6 +356,17 @@ def presolve_rays(rays):
     return res.astype(bool), t, ids
 
 
+def presolve_shadow_rays(pq, light_ids):
+    """k_shade's presolve of shadow rays on the device
+    (wpt_presolve_shadow_rays): per {p, q} pair and light shape id, whether
+    the ray provably ends unoccluded."""
+    p = np.ascontiguousarray(pq, dtype=np.float32).reshape(-1, 6)
+    li = np.ascontiguousarray(light_ids, dtype=np.int32)
+    res = np.zeros(p.shape[0], dtype=np.uint8)
+    _check(lib().wpt_presolve_shadow_rays(p.shape[0], p.ctypes.data, li.ctypes.data, res.ctypes.data))
+    return res.astype(bool)
+
+
 def shutdown():
     _check(lib().wpt_shutdown())
 
@@ -409,6 +422,22 @@ class DebugScene:
         _check(lib().wpt_debug_scene_presolve(self.h, n, r.ctypes.data, res.ctypes.data, t.ctypes.data,
                                               ids.ctypes.data))
         return res.astype(bool), t, ids
+
+    def presolve_shadow(self, pq, light_ids):
+        """The shadow presolve's host restatement (as presolve_shadow_rays, no GPU)."""
+        p = np.ascontiguousarray(pq, dtype=np.float32).reshape(-1, 6)
+        li = np.ascontiguousarray(light_ids, dtype=np.int32)
+        res = np.zeros(p.shape[0], dtype=np.uint8)
+        _check(lib().wpt_debug_scene_presolve_shadow(self.h, p.shape[0], p.ctypes.data, li.ctypes.data,
+                                                     res.ctypes.data))
+        return res.astype(bool)
+
+    def guard_lights(self):
+        """(bit mask of the light guards, shape ids of their primitives)."""
+        m, n = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        ids = np.full(4, -1, dtype=np.int32)
+        _check(lib().wpt_debug_scene_guard_lights(self.h, ctypes.addressof(m), ctypes.addressof(n), ids.ctypes.data))
+        return m.value, ids[: n.value].copy()
 
     def guards(self):
         """(root box (6,), guard boxes (n, 6), per-node guard of a leaf or 0xFFFFFFFF)."""
