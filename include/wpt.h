@@ -273,7 +273,9 @@ int wpt_seq_sum_device(const float* v, uint64_t n, float* out);
  * out[41] = of out[40], the rays resolved to a miss that adds nothing to their
  * path and so never written to a ray stream (WPT_OPT_DROP_MISS),
  * out[42] = of shadow rays, those their producer resolved as unoccluded and
- * added itself, never fed to a traversal kernel (WPT_OPT_PRESOLVE_SHADOW).
+ * added itself, never fed to a traversal kernel (WPT_OPT_PRESOLVE_SHADOW),
+ * out[43] = of out[40], the primary rays k_generate_shade resolved and shaded
+ * itself, never written to a ray stream (WPT_OPT_GEN_SHADE).
  * Visit/test/byte/iteration counts are only gathered with counting on. */
 int wpt_stats(uint64_t* out, size_t n);
 /* per-kernel device time (profiling on): out[0..11] = {ms, launches} ×
@@ -348,6 +350,10 @@ int wpt_set_lanes(int32_t n);
                                     provably ends unoccluded (no plane before the light, every guard box missed or behind
                                     it, no other light-guard triangle hit) and write it to no stream; 0: every shadow ray
                                     is traversed. Effective only where WPT_OPT_PRESOLVE is; the frame is the same bits. */
+#define WPT_OPT_GEN_SHADE 40     /* 1 (default): batches that presolve, other than PNEE and stock batches, generate their paths
+                                    with k_generate_shade: a primary ray it resolves (WPT_OPT_PRESOLVE) is shaded at once, from
+                                    registers, instead of being written to the back of stream 0 and read back by k_shade(0);
+                                    0: k_generate_ps and k_shade as before. The frame and every count are the same bits. */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */

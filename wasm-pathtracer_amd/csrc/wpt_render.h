@@ -101,6 +101,7 @@ struct Stats {
   uint64_t presolved_rays = 0;   // of rays: resolved by their producer (wpt_presolve.h), never fed to k_extend / k_trace
   uint64_t dropped_rays = 0;     // of presolved_rays: resolved to a miss that adds nothing, never written to a stream (WPT_OPT_DROP_MISS)
   uint64_t shadow_presolved_rays = 0;  // of shadow_rays: resolved unoccluded by k_shade, never fed to k_shadow / k_trace (WPT_OPT_PRESOLVE_SHADOW)
+  uint64_t gen_shaded_rays = 0;  // of presolved_rays: primary rays shaded by k_generate_shade, never written to a stream (WPT_OPT_GEN_SHADE)
 };
 
 // Kernel-time accumulators (ms), filled when profiling is on.
@@ -155,8 +156,14 @@ constexpr size_t kResWord = kFinishWord + 4;     // k_finish: rays, shadow rays,
 // shadow rays. (k_shade reaches it from the append counter: kShResWord - 2
 // words past append_ctr(b).)
 constexpr size_t kShResWord = kResWord + 2 * ((size_t)kMaxBounces + 1);
-constexpr size_t kCountWords = kShResWord + 2 * ((size_t)kMaxBounces + 1);
-static_assert(kResWord % 2 == 0 && kShResWord % 2 == 0, "the presolved counts are 64-bit slots");
+// after those: one 64-bit slot whose low word counts the primary rays that
+// k_generate_shade resolved and shaded itself (WPT_OPT_GEN_SHADE): they are in
+// no stream, so the device never reads it; the host adds it to bounce 0's rays
+// and to the presolved rays.
+constexpr size_t kGenShadeWord = kShResWord + 2 * ((size_t)kMaxBounces + 1);
+constexpr size_t kCountWords = kGenShadeWord + 2;
+static_assert(kResWord % 2 == 0 && kShResWord % 2 == 0 && kGenShadeWord % 2 == 0,
+              "the presolved counts are 64-bit slots");
 constexpr uint32_t kWorkWords = 16;   // device work counters (COUNT builds), see d_work_
 constexpr uint32_t kWorkCopies = 64;  // copies of them, one per blockIdx % 64 (spreads the atomics)
 struct PathSet {
@@ -577,6 +584,8 @@ class Renderer {
   bool presolve_ = true;           // WPT_OPT_PRESOLVE: producers resolve plane-or-miss extension rays (wpt_presolve.h)
   bool drop_miss_ = true;          // WPT_OPT_DROP_MISS: a ray resolved to a miss that adds nothing is not written to the next stream
   bool presolve_shadow_ = true;    // WPT_OPT_PRESOLVE_SHADOW: k_shade adds the contribution of a shadow ray it resolves unoccluded
+  bool gen_shade_ = true;          // WPT_OPT_GEN_SHADE: k_generate_shade shades the primary rays it resolves (bounce 0 of them in no stream)
+  uint32_t gen_shade_occ_[2] = {};  // k_generate_shade<TRI_ONLY>: resident blocks per CU (0: not yet queried)
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
   uint32_t probe_cap_ = 0, probe_waves_ = 0, probe_used_ = 0;

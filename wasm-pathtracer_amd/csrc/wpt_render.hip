@@ -1686,6 +1686,206 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
   }
 }
 
+// Generate + shade (WPT_OPT_GEN_SHADE): k_generate_ps and bounce 0 of k_shade's
+// presolving NEE variant in one launch, for the primary rays their producer
+// resolves. k_generate_ps writes such a ray to the back of stream 0 (48 B and
+// its 8 B hit record) and k_shade(0) reads the same 56 B back to shade values
+// the producer held in registers: origin = the camera, throughput (1, 1, 1),
+// (t, id) from presolve_ray. Here a resolved primary ray is shaded at once, by
+// the same shade_path on those operands, and goes to no stream: the back of
+// stream 0 stays empty (the low word of res_ctr(0) stays 0), and the ray is
+// counted in the slot at kGenShadeWord, which the host adds to bounce 0's rays
+// and to the presolved rays. Unresolved primary rays go to the front of stream
+// 0 through count0 as in k_generate_ps; k_extend(0) and k_shade(0) see only
+// those. A primary ray resolved to a miss that adds nothing (P.drop_miss) is
+// only counted, in the high word of res_ctr(0), as k_generate_ps does.
+// What a shaded path emits is handled as k_shade<.., PS = true>(0) handles it,
+// through the counters that launch appends to afterwards for its own paths:
+// the next ray is presolved (front or back of stream 1, its record to t_nx /
+// id_nx, or dropped), the shadow ray goes to the bounce-0 shadow stream or,
+// when presolve_shadow resolves it, is added to col here. One block scan and
+// ONE atomic instruction per kShadeBlock paths (lanes kWaves-1 .. kWaves+4, six
+// addresses; a lane whose increment is 0 stays out): count0, append_ctr(0),
+// the next bounce's presolved slot, the bounce's slot at kShResWord, the
+// dropped primaries and the shaded ones.
+// The order of a path's additions to col is unchanged: col[path] is 0 when
+// its primary ray is shaded, shade_path adds to col only when it emits no
+// shadow ray, a shadow ray resolved here is added in this launch, and an
+// unresolved one by k_shadow(0) or k_trace(1), both before k_shade(1), the
+// next launch that adds to the path. Blocks append in completion order, before
+// k_shade(0)'s blocks; a path's result does not depend on its position.
+// Not for PNEE batches (the octree staging belongs to k_shade) nor stock
+// batches (the CR count word): those run k_generate_ps.
+#ifndef WPT_GEN_SHADE_ONESHOT
+#define WPT_GEN_SHADE_ONESHOT 0  // 1: one block per kShadeBlock paths instead of the persistent grid (experiment builds)
+#endif
+template <bool TRI_ONLY>
+__global__ void __launch_bounds__(kShadeBlock) k_generate_shade(GenParams G, const uint32_t* __restrict__ part_pix,
+                                                                uint64_t k0, uint32_t n, uint32_t* __restrict__ pix_out,
+                                                                float4* __restrict__ col,
+                                                                const uint32_t* __restrict__ rnd_off,
+                                                                const uint32_t* __restrict__ rnd_base,
+                                                                const uint32_t* __restrict__ rnd_list, DevScene S,
+                                                                ShadeParams P, RayStream s0, RayStream out,
+                                                                ShadowStream sh, float* __restrict__ t_nx,
+                                                                int32_t* __restrict__ id_nx,
+                                                                uint32_t* __restrict__ counts) {
+  constexpr uint32_t kWaves = kShadeBlock / 64;
+  static_assert(kWaves + 4 < 64, "the scan's totals and the other atomic lanes sit in one wave");
+  static_assert(kShadeBlock < 1024, "10-bit fields in the scan's packed columns");
+  // columns: unresolved primaries | survivors (front) | streamed shadow rays |
+  // next rays resolved, dropped << 10, shadow rays resolved << 20 |
+  // primaries dropped, shaded << 10
+  __shared__ uint32_t s_off[5][kWaves];
+  __shared__ f4v s_light[5 * kShadeLights];
+  const bool lds_lights = S.num_lights <= kShadeLights;
+  if (lds_lights) {
+    for (uint32_t k = threadIdx.x; k < 5 * S.num_lights; k += kShadeBlock) {
+      const float4 v = S.lights[k];
+      s_light[k] = f4v{v.x, v.y, v.z, v.w};
+    }
+  }
+  __syncthreads();  // the light records
+  OctG O;
+  O.child = S.oct_child;
+  O.cum = S.oct_cum;
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const V3 bg = mk(S.bg[0], S.bg[1], S.bg[2]);
+  const V3 add_c = mulv(mk(1.0f, 1.0f, 1.0f), bg);  // shade_path's miss branch
+  const bool adds_nothing =
+      P.drop_miss != 0 && (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+  for (uint32_t i0 = blockIdx.x * kShadeBlock; i0 < n; i0 += gridDim.x * kShadeBlock) {  // block-uniform
+    const uint32_t i = i0 + threadIdx.x;
+    ShadeOut R;
+    R.alive = R.shadow = false;
+    bool front0 = false, drop0 = false, shaded = false;
+    if (i < n) {
+      const GenPath g = gen_path(G, part_pix, k0 + i, rnd_off, rnd_base, rnd_list);
+      pix_out[i] = rnd_off ? g.pl : g.pixel;
+      col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      float t = 0.0f;
+      int32_t id = -1;
+      const bool res0 = presolve_ray(S, *S.pre, mk(G.cam[0], G.cam[1], G.cam[2]), g.v, t, id);
+      const float4 o4 = make_float4(G.cam[0], G.cam[1], G.cam[2], __uint_as_float(g.s));  // w: the path's rng state
+      const float4 d4 = make_float4(g.v.x, g.v.y, g.v.z, __uint_as_float(i));            // w: the path's index in the batch
+      const float4 th4 = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(g.type << kTypeShift));
+      if (!res0) {
+        // to the front of stream 0 (R's extension ray holds it until the scan)
+        front0 = true;
+        R.ro = o4;
+        R.rd = d4;
+        R.th = th4;
+      } else if (id < 0 && adds_nothing) {
+        drop0 = true;
+      } else {
+        shaded = true;
+        shade_path<TRI_ONLY, false, OctG, false>(S, O, P, col, t, id, o4, d4, th4, R,
+                                                 lds_lights ? (const lds_f4v*)s_light : nullptr);
+      }
+    }
+    // from here on as k_shade<.., PS = true> after its shade_path
+    bool res = false;
+    float pt = 0.0f;
+    int32_t pid = -1;
+    if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
+    bool drop = false;
+    if (res && pid < 0 && P.drop_miss) {
+      const V3 ac = mulv(ld3(R.th), bg);  // shade_path's miss branch
+      drop = (__float_as_uint(ac.x) | __float_as_uint(ac.y) | __float_as_uint(ac.z)) == 0u;
+    }
+    if (drop) R.alive = res = false;
+    bool sres = false;
+    if (R.shadow && P.presolve_shadow)
+      sres = presolve_shadow(S, *S.pre, ld3(R.so), ld3(R.sd), R.so.w, (int32_t)__float_as_uint(R.sd.w));
+    const uint64_t fm = __ballot(front0), am = __ballot(R.alive && !res), sm = __ballot(R.shadow && !sres);
+    const uint64_t rm = __ballot(res), dm = __ballot(drop), zm = __ballot(sres);
+    const uint64_t d0m = __ballot(drop0), g0m = __ballot(shaded);
+    if (lane == 0) {
+      s_off[0][wid] = (uint32_t)__popcll(fm);
+      s_off[1][wid] = (uint32_t)__popcll(am);
+      s_off[2][wid] = (uint32_t)__popcll(sm);
+      s_off[3][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 10) | ((uint32_t)__popcll(zm) << 20);
+      s_off[4][wid] = (uint32_t)__popcll(d0m) | ((uint32_t)__popcll(g0m) << 10);
+    }
+    __syncthreads();
+    if (wid == 0) {
+      const bool in = lane < kWaves;
+      const uint32_t f = in ? s_off[0][lane] : 0u, a = in ? s_off[1][lane] : 0u, b = in ? s_off[2][lane] : 0u;
+      const uint32_t c = in ? s_off[3][lane] : 0u, e = in ? s_off[4][lane] : 0u;
+      uint32_t jf = f, ia = a, ib = b, ic = c, ie = e;
+#pragma unroll
+      for (uint32_t k = 1; k < kWaves; k <<= 1) {
+        const uint32_t yf = __shfl_up(jf, k, 64), ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64);
+        const uint32_t yc = __shfl_up(ic, k, 64), ye = __shfl_up(ie, k, 64);
+        if (lane >= k) { jf += yf; ia += ya; ib += yb; ic += yc; ie += ye; }
+      }
+      // lane kWaves - 1 holds every total
+      const uint32_t tf = (uint32_t)__shfl((int)jf, (int)(kWaves - 1), 64);
+      const uint32_t tc = (uint32_t)__shfl((int)ic, (int)(kWaves - 1), 64);
+      const uint32_t te = (uint32_t)__shfl((int)ie, (int)(kWaves - 1), 64);
+      // this lane's counter (u32 index in counts) and increment
+      uint32_t word = 2u;  // append_ctr(0): survivors | streamed shadow rays
+      unsigned long long inc = (unsigned long long)ia | ((unsigned long long)ib << 32);
+      if (lane == kWaves) {  // res_ctr(1): next rays resolved | dropped
+        word = (uint32_t)kResWord + 2u;
+        inc = (unsigned long long)(tc & 0x3ffu) | ((unsigned long long)((tc >> 10) & 0x3ffu) << 32);
+      } else if (lane == kWaves + 1) {  // bounce 0's shadow rays resolved here
+        word = (uint32_t)kShResWord;
+        inc = (unsigned long long)(tc >> 20);
+      } else if (lane == kWaves + 2) {  // count0 (the word after it is unused)
+        word = 0u;
+        inc = (unsigned long long)tf;
+      } else if (lane == kWaves + 3) {  // res_ctr(0)'s high word: primaries dropped
+        word = (uint32_t)kResWord;
+        inc = (unsigned long long)(te & 0x3ffu) << 32;
+      } else if (lane == kWaves + 4) {  // primaries shaded here
+        word = (uint32_t)kGenShadeWord;
+        inc = (unsigned long long)(te >> 10);
+      }
+      unsigned long long base = 0ull;
+      if (lane >= kWaves - 1 && lane <= kWaves + 4 && inc != 0ull)
+        base = atomicAdd(reinterpret_cast<unsigned long long*>(counts + word), inc);
+      const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
+      const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
+      const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
+      const uint32_t bf = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves + 2), 64);
+      if (in) {
+        s_off[0][lane] = bf + jf - f;
+        s_off[1][lane] = ba + ia - a;
+        s_off[2][lane] = bb + ib - b;
+        s_off[3][lane] = bc + ((ic - c) & 0x3ffu);
+      }
+    }
+    __syncthreads();
+    if (front0) {
+      const uint32_t p = s_off[0][wid] + (uint32_t)__popcll(fm & below);
+      s0.thr[p] = R.th;
+      s0.o[p] = R.ro;
+      s0.d[p] = R.rd;
+    } else if (R.alive) {
+      uint32_t p = s_off[1][wid] + (uint32_t)__popcll(am & below);
+      if (res) p = n - 1u - (s_off[3][wid] + (uint32_t)__popcll(rm & below));
+      st_stream(out.o + p, R.ro);
+      st_stream(out.d + p, R.rd);
+      st_stream(out.thr + p, R.th);
+      if (res) {
+        t_nx[p] = pt;
+        id_nx[p] = pid;
+      }
+    }
+    if (sres) {
+      add_contribution_xyz(col, R.sc);
+    } else if (R.shadow) {
+      const uint32_t p = s_off[2][wid] + (uint32_t)__popcll(sm & below);
+      st_stream(sh.o + p, R.so);
+      st_stream(sh.d + p, R.sd);
+      st_stream(sh.c + p, R.sc);
+    }
+    __syncthreads();  // s_off is rewritten by the next iteration
+  }
+}
+
 // Wave-interleaved work feed of the persistent traversal kernels. The stream
 // is cut into kFeedChunk-entry chunks; wave w of W owns chunks w, w+W, w+2W, ... and
 // its idle lanes take the wave's next entries in lane order (ballot + prefix
@@ -2756,6 +2956,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 37: if (!range(0, 1)) return false; presolve_ = v != 0; return true;
     case 38: if (!range(0, 1)) return false; drop_miss_ = v != 0; return true;
     case 39: if (!range(0, 1)) return false; presolve_shadow_ = v != 0; return true;
+    case 40: if (!range(0, 1)) return false; gen_shade_ = v != 0; return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -2810,6 +3011,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 37: v = presolve_ ? 1 : 0; return true;
     case 38: v = drop_miss_ ? 1 : 0; return true;
     case 39: v = presolve_shadow_ ? 1 : 0; return true;
+    case 40: v = gen_shade_ ? 1 : 0; return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -3069,8 +3271,11 @@ static void add_counts(Stats& st, const uint32_t* hc, int b, bool stock, bool pr
     // (a batch that presolves nothing neither clears nor copies those words)
     // the slot's high word: of the resolved ones, those dropped (in no stream)
     const uint32_t drop = presolve ? hc[kResWord + 2 * i + 1] : 0u;
-    const uint64_t res = (uint64_t)(presolve ? hc[kResWord + 2 * i] : 0u) + drop;
+    // bounce 0: and the primary rays k_generate_shade shaded itself (in no stream)
+    const uint32_t gsh = presolve && i == 0 ? hc[kGenShadeWord] : 0u;
+    const uint64_t res = (uint64_t)(presolve ? hc[kResWord + 2 * i] : 0u) + drop + gsh;
     r += (i == 0 ? hc[0] : hc[2 + 2 * (i - 1)]) + res;
+    st.gen_shaded_rays += gsh;
     // the shadow rays k_shadow / k_trace saw plus those k_shade resolved
     const uint32_t sres = presolve ? hc[kShResWord + 2 * i] : 0u;
     sr += (uint64_t)hc[3 + 2 * i] + sres;
@@ -3127,6 +3332,12 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   // RR-only batches (the k_finish hand-over reads one live count per lane)
   // run without the presolve
   B.presolve = presolve_ && max_depth_ > 0 && num_guards_ != 0;
+  B.pnee = left_type_ == 2 || right_type_ == 2;
+  // k_generate_shade shades the primary rays it resolves (WPT_OPT_GEN_SHADE);
+  // PNEE batches (k_shade stages the octree) and stock batches (the count
+  // word) keep k_generate_ps. SP: batch_advance's.
+  const bool gen_shade = gen_shade_ && B.presolve && !B.pnee && !B.stock;
+  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
   if (profiling_ && !B.async) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
   for (int i = 0; i < B.nl; i++) {
@@ -3147,7 +3358,29 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
     const uint32_t nn = (uint32_t)C.paths;
     // (the presolved counts, the words from kResWord on, only where they are used)
     HIP_OK(hipMemsetAsync(L.counts, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), s));
-    if (B.presolve)
+    if (gen_shade) {
+      // a persistent grid, as k_shade's: the variant's own occupancy
+      const int ti = ds_.tri_only ? 1 : 0;
+      if (gen_shade_occ_[ti] == 0) {
+        int bpc = 0;
+        if (ti) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_generate_shade<true>, (int)kShadeBlock, 0));
+        else HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_generate_shade<false>, (int)kShadeBlock, 0));
+        gen_shade_occ_[ti] = (uint32_t)std::max(bpc, 1);
+      }
+      const uint32_t tiles = std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock);
+      const uint32_t gg = WPT_GEN_SHADE_ONESHOT || (C.async && async_oneshot_)
+                              ? tiles
+                              : std::min<uint32_t>(tiles, (uint32_t)ncu_ * gen_shade_occ_[ti]);
+      const RayStream s0{L.ro[0], L.rd[0], L.thr[0]};
+      const RayStream s1{L.ro[1], L.rd[1], L.thr[1]};
+      const ShadowStream sh{L.so, L.sd, L.sc};
+#define WPT_GENSH(T)                                                                                                 \
+  k_generate_shade<T><<<gg, kShadeBlock, 0, s>>>(G, part, B.k0 + B.off[i], nn, L.pixel, L.col, rnd_off, rnd_base, \
+                                                 B.mlist, ds_, SP, s0, s1, sh, L.hit_t(1), L.hit_id(1), L.counts)
+      if (ti) LAUNCH_TIMED(C, 0, generate, n_generate, WPT_GENSH(true));
+      else LAUNCH_TIMED(C, 0, generate, n_generate, WPT_GENSH(false));
+#undef WPT_GENSH
+    } else if (B.presolve)
       LAUNCH_TIMED(C, 0, generate, n_generate,
                    k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, s>>>(
                        G, part, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, rnd_off,
@@ -3164,7 +3397,6 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   // shadow rays (k_trace); the last bounce's shadow rays follow the loop
   B.fused = (fused_ || B.n < (B.async && async_fused_below_ ? async_fused_below_ : fused_below_)) && trav_ext_ != 1 &&
             trav_sh_ != 1;
-  B.pnee = left_type_ == 2 || right_type_ == 2;
   B.b = 0;
   B.finished = false;
   B.state = Batch::kBouncing;
@@ -4194,6 +4426,8 @@ bool Renderer::launch_extend(const LaunchCtx& C, const float4* ro, const float4*
 #undef WPT_EXT
   if (ds.probe && C.probe_res) {
     k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
+    // bounce 0: and the primary rays k_generate_shade shaded (one more word, 0 without it)
+    if (C.bounce == 0) k_probe_add_sh<<<1, 1, 0, C.stream>>>(ds.probe, L.counts + kGenShadeWord);
     HIP_OK(hipGetLastError());
   }
   return true;

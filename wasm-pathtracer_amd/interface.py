@@ -226,7 +226,7 @@ def stats():
             "finish_paths", "finish_max_bounces", "max_ray_visits", "ex_body_lanes", "ex_bodies", "lf_body_lanes",
             "lf_bodies", "stock_traced", "stock_deficit", "stock_waits", "plan_us", "stock_us",
             "stock_rays", "stock_rays_used", "presolved_rays", "dropped_rays",
-            "shadow_presolved_rays")
+            "shadow_presolved_rays", "gen_shaded_rays")
     out = (ctypes.c_uint64 * len(keys))()
     _check(lib().wpt_stats(ctypes.addressof(out), len(keys)))
     return dict(zip(keys, list(out)))
@@ -272,7 +272,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "fill": 25, "async_prio": 26, "async_grid_pct": 27, "scene_traversal": 28, "scene_tri_only": 29,
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
-           "presolve_shadow": 39}
+           "presolve_shadow": 39, "gen_shade": 40}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
