@@ -165,6 +165,35 @@ int64_t wpt_tile_partition(uint32_t width, uint32_t height, uint32_t rank, uint3
  * cum[node * num_lights + light] (cum_bins) and shot_stored[2]. */
 int64_t wpt_photon_tree(uint32_t* child, float* cum, uint64_t* shot_stored);
 
+/* Host-only (no session, no GPU): the frozen octree of a caller's photon list
+ * (light id < num_lights, location xyz, intensity; inserted in this order).
+ * Returns the node count; fills (each may be NULL: size query) child and cum
+ * as wpt_photon_tree does, and corners[64 * node + 8 * case + c], the table of
+ * the 8 cells of the device's trilinear mix per leaf and offset case (x, y, z
+ * offset +1: bits 2, 1, 0 of the case; corner c: bit 2 x, bit 1 y, bit 0 z
+ * shifted to the adjacent cell, clamped to the root box). Internal nodes and
+ * leaves deeper than 20 levels have zero rows: the device finds their cells by
+ * descents. WPT_ERR_INVALID_ARG for a light id out of range. */
+int64_t wpt_photon_build(uint32_t num_lights, uint64_t n, const uint32_t* light, const float* loc3,
+                         const float* intensity, uint32_t* child, float* cum, uint32_t* corners);
+
+/* Test hook: the photon list as the session's PNEE octree, for the scene's
+ * light count, frozen and uploaded as a shot tree is. It stays until what
+ * drops a shot tree drops it (a new scene, a new frame seed); the session then
+ * shoots its own again. WPT_ERR_INVALID_ARG for a light id >= the light
+ * count. */
+int wpt_install_photons(uint64_t n, const uint32_t* light, const float* loc3, const float* intensity);
+
+/* Test hook: the device's PhotonTree::sample (photon_tree.rs:80-159) on the
+ * session's octree, point i (points3[3 i ..]) on the xorshift32 state
+ * states[i]: the light picked, its pdf and the state afterwards. view: where
+ * the kernel reads the tree, as the shade kernel's three variants do (0 global
+ * memory, 1 child array in LDS, 2 child array and CDFs in LDS);
+ * WPT_ERR_INVALID_ARG if the tree does not fit it. table 0: the neighbour
+ * cells by walks only, not from the corner table. */
+int wpt_photon_sample(size_t n, const float* points3, const uint32_t* states, int32_t view, int32_t table,
+                      uint32_t* light, float* pdf, uint32_t* states_out);
+
 /* Accumulated radiance: acc3 = width*height*3 f32 (sum over samples, as
  * RenderTarget.acc_buffer), cnt = width*height u32 (acc_count). */
 int wpt_read_radiance(float* acc3, uint32_t* cnt);
@@ -357,7 +386,9 @@ int wpt_set_lanes(int32_t n);
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
-#define WPT_OPT_SCENE_TRI_ONLY 29  /* read-only: 1 if the scene's finite shapes are all triangles (-1 no scene) */
+#define WPT_OPT_OCT_VIEW 41      /* read-only: where the shade kernel reads the session's PNEE octree: 0 global memory, 1 child
+                                    array in LDS, 2 child array and CDFs in LDS (-1 no tree yet) */
+#define WPT_OPT_SCENE_TRI_ONLY 29 /* read-only: 1 if the scene's finite shapes are all triangles (-1 no scene) */
 int wpt_set_option(int32_t option, int64_t value);
 /* Wave timelines of the traversal launches recorded since WPT_OPT_PROBE was
  * set (measurement only; the probe costs a clock read per wave and per feed

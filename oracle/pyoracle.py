@@ -53,6 +53,10 @@ def lib():
         L.oracle_adaptive_free.argtypes = [c_p]
         L.oracle_photon_tree.restype = c_sz
         L.oracle_photon_tree.argtypes = [c_p, c_u32, c_int, c_p, c_p, c_p]
+        L.oracle_set_photons.argtypes = [c_p, c_sz, c_p, c_p, c_p]
+        L.oracle_clear_photons.argtypes = [c_p]
+        L.oracle_photon_sample.argtypes = [c_p, c_u32, c_int, c_sz, c_p, c_p, c_p, c_p, c_p]
+        L.oracle_photon_leaf.argtypes = [c_p, c_u32, c_int, c_sz, c_p, c_p, c_p]
         _L = L
     return _L
 
@@ -153,6 +157,44 @@ class OracleScene:
         counts = np.empty(2, dtype=np.uint64)
         L.oracle_photon_tree(self.h, seed, threads, leafs.ctypes.data, cum.ctypes.data, counts.ctypes.data)
         return leafs, cum[: n * self.num_lights].reshape(n, self.num_lights), int(counts[0]), int(counts[1])
+
+    def set_photons(self, photons):
+        """Install a photon list (light ids, locations (n, 3), intensities, in
+        insertion order) as this scene's PNEE tree: render(), photon_tree() and
+        the pointwise queries use it for every seed until clear_photons()."""
+        light, loc, intensity = photons
+        li = np.ascontiguousarray(light, dtype=np.uint32)
+        lo = np.ascontiguousarray(loc, dtype=np.float32).reshape(-1, 3)
+        it = np.ascontiguousarray(intensity, dtype=np.float32)
+        assert li.shape[0] == lo.shape[0] == it.shape[0]
+        assert li.size == 0 or int(li.max()) < self.num_lights
+        lib().oracle_set_photons(self.h, li.shape[0], li.ctypes.data, lo.ctypes.data, it.ctypes.data)
+
+    def clear_photons(self):
+        lib().oracle_clear_photons(self.h)
+
+    def photon_sample(self, points, states, seed=0xBABABEBE, threads=8):
+        """PhotonTree::sample of points (n, 3), point i on the xorshift32 state
+        states[i]: (light, pdf, state after) per point."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(states, dtype=np.uint32)
+        n = p.shape[0]
+        assert s.shape == (n,)
+        light = np.empty(n, dtype=np.uint32)
+        pdf = np.empty(n, dtype=np.float32)
+        out = np.empty(n, dtype=np.uint32)
+        lib().oracle_photon_sample(self.h, seed, threads, n, p.ctypes.data, s.ctypes.data, light.ctypes.data,
+                                   pdf.ctypes.data, out.ctypes.data)
+        return light, pdf, out
+
+    def photon_leaf(self, points, seed=0xBABABEBE, threads=8):
+        """find_leaf per point: (depth (n,), bounds (n, 6) = mins then maxes)."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        depth = np.empty(n, dtype=np.uint32)
+        bounds = np.empty((n, 6), dtype=np.float32)
+        lib().oracle_photon_leaf(self.h, seed, threads, n, p.ctypes.data, depth.ctypes.data, bounds.ctypes.data)
+        return depth, bounds
 
     def __del__(self):
         try:

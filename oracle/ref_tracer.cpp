@@ -301,7 +301,9 @@ struct OracleHandle {
   Scene scene;
   std::unique_ptr<PhotonTree> photons;  // PNEE tree for photon_seed_of
   uint32_t photon_seed_of = 0;
+  std::unique_ptr<PhotonTree> installed;  // a caller's photon list: replaces the shot tree for every seed
   PhotonTree* photon_tree(uint32_t seed, int threads) {
+    if (installed) return installed.get();
     if (!photons || photon_seed_of != seed) {
       photons = std::make_unique<PhotonTree>(scene.lights.size());
       shoot_photons(scene, seed, threads, *photons);
@@ -545,6 +547,50 @@ size_t oracle_photon_tree(void* p, uint32_t seed, int threads, uint8_t* leafs, f
   if (cum) memcpy(cum, c.data(), sizeof(float) * c.size());
   if (counts) { counts[0] = t->shot; counts[1] = t->num_photons; }
   return l.size();
+}
+
+// A caller's photon list (PhotonTree::insert in this order) as the handle's
+// tree: oracle_render's PNEE halves, oracle_photon_tree and the two queries
+// below use it for every seed until oracle_clear_photons.
+void oracle_set_photons(void* p, size_t n, const uint32_t* light, const float* loc3, const float* intensity) {
+  OracleHandle* h = (OracleHandle*)p;
+  auto t = std::make_unique<PhotonTree>(h->scene.lights.size());
+  for (size_t i = 0; i < n; i++) t->insert(light[i], v3(loc3[3 * i], loc3[3 * i + 1], loc3[3 * i + 2]), intensity[i]);
+  t->root->freeze();
+  h->installed = std::move(t);
+}
+void oracle_clear_photons(void* p) { ((OracleHandle*)p)->installed.reset(); }
+
+// PhotonTree::sample (photon_tree.rs:80-159) of point i on the xorshift32
+// state states[i]: light, pdf, state afterwards.
+void oracle_photon_sample(void* p, uint32_t seed, int threads, size_t n, const float* pts3, const uint32_t* states,
+                          uint32_t* light, float* pdf, uint32_t* states_out) {
+  PhotonTree* t = ((OracleHandle*)p)->photon_tree(seed, threads);
+  for (size_t i = 0; i < n; i++) {
+    Rng rng;
+    rng.state = states[i];
+    size_t li = 0;
+    float pd = 0.0f;
+    t->sample(rng, v3(pts3[3 * i], pts3[3 * i + 1], pts3[3 * i + 2]), &li, &pd);
+    light[i] = (uint32_t)li;
+    pdf[i] = pd;
+    states_out[i] = rng.state;
+  }
+}
+
+// find_leaf (photon_tree.rs:209-220) per point: the leaf's depth and bounds
+// (x_min, y_min, z_min, x_max, y_max, z_max).
+void oracle_photon_leaf(void* p, uint32_t seed, int threads, size_t n, const float* pts3, uint32_t* depth,
+                        float* bounds6) {
+  PhotonTree* t = ((OracleHandle*)p)->photon_tree(seed, threads);
+  for (size_t i = 0; i < n; i++) {
+    Box6 b;
+    size_t d = 0;
+    t->root->find_leaf(t->bounds(), 0, v3(pts3[3 * i], pts3[3 * i + 1], pts3[3 * i + 2]), &b, &d);
+    depth[i] = (uint32_t)d;
+    const float o[6] = {b.x_min, b.y_min, b.z_min, b.x_max, b.y_max, b.z_max};
+    memcpy(bounds6 + 6 * i, o, sizeof o);
+  }
 }
 
 // ---------------------------------------------------------------------------

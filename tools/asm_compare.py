@@ -1,0 +1,49 @@
+"""Compares two device assembly listings of wpt_render.hip (`make -C
+wasm-pathtracer_amd/csrc asm` gives build/wpt_render.s) function by function:
+the instructions, the kernel descriptor and the register counts of every
+function of the first listing must be in the second unchanged. Block and
+function label numbers, which shift when a function is added, are ignored.
+Prints the functions only the second listing has; exit 1 on a difference.
+Usage: python3 tools/asm_compare.py PARENT.s NEW.s"""
+import re
+import sys
+
+
+def functions(path):
+    txt = open(path).read()
+    chunks = re.split(r"^\.Lfunc_end\d+:\n", txt, flags=re.M)
+    out = {}
+    for i, c in enumerate(chunks[:-1]):
+        name = re.findall(r"^(_Z\w+):", c, re.M)[-1]
+        body = c[c.rindex("\n" + name + ":"):]
+        # the resource counts (.set NAME.num_vgpr ...) follow the end label
+        meta = "\n".join(l for l in chunks[i + 1].split("\n")[:40] if l.startswith("\t.set " + name + "."))
+        out[name] = body + meta
+    return out
+
+
+def norm(body):
+    body = re.sub(r"\.LBB\d+_", ".LBB_", body)
+    body = re.sub(r"\.Lfunc_(begin|end)\d+", ".Lfunc_", body)
+    return re.sub(r"\.Ltmp\d+", ".Ltmp", body)
+
+
+def main():
+    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    missing = [k for k in a if k not in b]
+    differ = [k for k in a if k in b and norm(a[k]) != norm(b[k])]
+    lines = sum(len(v.splitlines()) for v in a.values())
+    print(f"functions: first {len(a)} ({lines} lines), second {len(b)}; identical {len(a) - len(missing) - len(differ)}, "
+          f"different {len(differ)}, missing {len(missing)}")
+    for k in differ:
+        print("DIFFERS", k)
+    for k in missing:
+        print("MISSING", k)
+    for k in b:
+        if k not in a:
+            print("only in second:", k)
+    return 1 if differ or missing else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

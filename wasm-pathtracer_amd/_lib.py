@@ -40,6 +40,9 @@ _SIGS = {
     "wpt_partition_pixels": (ctypes.c_int64, [c_p]),
     "wpt_tile_partition": (ctypes.c_int64, [c_u32, c_u32, c_u32, c_u32, c_u32, c_p]),
     "wpt_photon_tree": (ctypes.c_int64, [c_p, c_p, c_p]),
+    "wpt_photon_build": (ctypes.c_int64, [c_u32, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "wpt_install_photons": (ctypes.c_int, [ctypes.c_uint64, c_p, c_p, c_p]),
+    "wpt_photon_sample": (ctypes.c_int, [c_sz, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
     "wpt_read_radiance": (ctypes.c_int, [c_p, c_p]),
     "wpt_copy_partition": (ctypes.c_int, [c_p]),
     "wpt_set_exchange": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.c_uint64]),

@@ -363,6 +363,45 @@ int64_t wpt_photon_tree(uint32_t* child, float* cum, uint64_t* shot_stored) {
   return (int64_t)c.size();
 }
 
+int64_t wpt_photon_build(uint32_t num_lights, uint64_t n, const uint32_t* light, const float* loc3,
+                         const float* intensity, uint32_t* child, float* cum, uint32_t* corners) {
+  if (n && (!light || !loc3 || !intensity)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  for (uint64_t i = 0; i < n; i++)
+    if (light[i] >= num_lights) return fail(WPT_ERR_INVALID_ARG, "photon light id out of range");
+  wpt::PhotonTree tree(num_lights);
+  for (uint64_t i = 0; i < n; i++) tree.insert(light[i], mk(loc3[3 * i], loc3[3 * i + 1], loc3[3 * i + 2]), intensity[i]);
+  std::vector<uint32_t> c, t;
+  std::vector<float> f;
+  tree.freeze(c, f);
+  if (child) memcpy(child, c.data(), sizeof(uint32_t) * c.size());
+  if (cum) memcpy(cum, f.data(), sizeof(float) * f.size());
+  if (corners) {
+    wpt::oct_corner_table(c, t);
+    memcpy(corners, t.data(), sizeof(uint32_t) * t.size());
+  }
+  return (int64_t)c.size();
+}
+
+int wpt_install_photons(uint64_t n, const uint32_t* light, const float* loc3, const float* intensity) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (n && (!light || !loc3 || !intensity)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  std::string err;
+  const int rc = g_session->renderer.install_photons(n, light, loc3, intensity, err);
+  if (rc <= 0) return fail(rc < 0 ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_photon_sample(size_t n, const float* points3, const uint32_t* states, int32_t view, int32_t table,
+                      uint32_t* light, float* pdf, uint32_t* states_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (n && (!points3 || !states || !light || !pdf || !states_out)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  if (view < 0 || view > 2) return fail(WPT_ERR_INVALID_ARG, "photon_sample: view 0, 1 or 2");
+  std::string err;
+  const int rc = g_session->renderer.photon_sample(n, points3, states, view, table != 0, light, pdf, states_out, err);
+  if (rc <= 0) return fail(rc < 0 ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 int wpt_read_radiance(float* acc3, uint32_t* cnt) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   if (!acc3) return fail(WPT_ERR_INVALID_ARG, "null buffer");

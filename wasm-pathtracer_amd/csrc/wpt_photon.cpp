@@ -57,4 +57,49 @@ void PhotonTree::freeze(std::vector<uint32_t>& child, std::vector<float>& cum) c
   }
 }
 
+void oct_corner_table(const std::vector<uint32_t>& child, std::vector<uint32_t>& corners) {
+  const size_t nn = child.size();
+  corners.assign(64 * nn, 0u);
+  auto walk = [&](uint32_t ix, uint32_t iy, uint32_t iz, int d) {
+    uint32_t node = 0;
+    for (int l = d - 1; l >= 0; l--) {
+      const uint32_t c = child[node];
+      if (c == 0u) break;
+      node = c + (((ix >> l) & 1u) << 2) + (((iy >> l) & 1u) << 1) + ((iz >> l) & 1u);
+    }
+    return node;
+  };
+  struct Item {
+    uint32_t node;
+    int d;
+    uint32_t kx, ky, kz;
+  };
+  std::vector<Item> todo{{0u, 0, 0u, 0u, 0u}};
+  while (!todo.empty()) {
+    const Item it = todo.back();
+    todo.pop_back();
+    const uint32_t c0 = child[it.node];
+    if (c0 != 0u) {
+      if (it.d < kOctLattice)
+        for (uint32_t j = 0; j < 8; j++)
+          todo.push_back({c0 + j, it.d + 1, 2 * it.kx + ((j >> 2) & 1u), 2 * it.ky + ((j >> 1) & 1u),
+                          2 * it.kz + (j & 1u)});
+      continue;
+    }
+    const int64_t last = ((int64_t)1 << it.d) - 1;
+    auto adj = [&](uint32_t k, int off) {
+      const int64_t a = (int64_t)k + off;
+      return (uint32_t)(a < 0 ? 0 : (a > last ? last : a));
+    };
+    for (uint32_t oc = 0; oc < 8; oc++) {
+      const uint32_t ax = adj(it.kx, (oc & 4u) ? 1 : -1), ay = adj(it.ky, (oc & 2u) ? 1 : -1),
+                     az = adj(it.kz, (oc & 1u) ? 1 : -1);
+      uint32_t* row = corners.data() + 64 * (size_t)it.node + 8 * oc;
+      row[0] = it.node;
+      for (uint32_t c = 1; c < 8; c++)
+        row[c] = walk((c & 4u) ? ax : it.kx, (c & 2u) ? ay : it.ky, (c & 1u) ? az : it.kz, it.d);
+    }
+  }
+}
+
 }  // namespace wpt

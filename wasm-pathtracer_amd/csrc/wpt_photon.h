@@ -20,6 +20,11 @@ namespace wpt {
 constexpr uint32_t kPhotonsNeeded = 300000;    // tracer.rs:104
 constexpr size_t kMaxPhotonsInCell = 1024;     // photon_tree.rs:31
 constexpr float kPhotonTreeSize = 1024.0f;     // photon_tree.rs:55
+// Depth up to which photon_sample (wpt_render.hip) addresses cells by their
+// integer lattice index, and so the depth of the deepest leaves that have a
+// row in the corner table.
+constexpr int kOctLattice = 20;
+constexpr uint32_t kOctLdsWords = 6144;  // PNEE octree words k_shade stages in LDS (24 KB per block)
 
 struct PhotonRec {
   uint32_t light;
@@ -51,6 +56,21 @@ class PhotonTree {
   size_t inserted_ = 0;
   std::vector<Node> nodes_;
 };
+
+// photon_sample's neighbour cells of a frozen tree, per leaf and offset case
+// (xo, yo, zo = -1 / +1 per axis: bits 2, 1, 0 of the case): corners[64 * leaf
+// + 8 * case + c] is the cell of corner c (bit 2 x, bit 1 y, bit 0 z shifted
+// to the adjacent lattice index, clamped to the root box), found by the walk
+// oct_walk does on the device from the leaf's lattice index. Leaves deeper
+// than kOctLattice and internal nodes keep zero rows.
+void oct_corner_table(const std::vector<uint32_t>& child, std::vector<uint32_t>& corners);
+
+// Words of a frozen tree k_shade copies to LDS (6 blocks per CU must still
+// fit): child and CDFs, else the child array alone, else none.
+inline uint32_t oct_lds_words(size_t nodes, size_t cum_words) {
+  const size_t all = nodes + cum_words;
+  return all <= kOctLdsWords ? (uint32_t)all : nodes <= kOctLdsWords ? (uint32_t)nodes : 0u;
+}
 
 // child() (photon_tree.rs:224-243): octant index and bounds of `v` in `b`
 // (x_min,y_min,z_min,x_max,y_max,z_max).

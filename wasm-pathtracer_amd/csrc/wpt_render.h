@@ -13,6 +13,7 @@
 #include <deque>
 #include <vector>
 
+#include "wpt_photon.h"
 #include "wpt_scene.h"
 #include "wpt_seqsum.h"
 
@@ -285,6 +286,15 @@ class Renderer {
   // octree on the host, upload it. Done lazily by compute() when a half of
   // the screen renders PNEE; `photon_tree` exposes the frozen tree.
   bool build_photons(std::string& err);
+  // Test hooks. install_photons: a caller's photon list (insertion order) as
+  // the session's tree, through build_photons' freeze + upload; whatever
+  // drops a shot tree drops it too. Returns -1 for a light id out of range.
+  // photon_sample: the device's PhotonTree::sample of n points, each on its
+  // own xorshift32 state, reading the tree as k_shade's OCT = `view` variant
+  // does (`table` false: no corner table); -1 if the tree does not fit.
+  int install_photons(size_t n, const uint32_t* light, const float* loc3, const float* intensity, std::string& err);
+  int photon_sample(size_t n, const float* pts3, const uint32_t* states, int view, bool table, uint32_t* light,
+                    float* pdf, uint32_t* states_out, std::string& err);
   bool photon_tree(std::vector<uint32_t>& child, std::vector<float>& cum, uint64_t& shot, uint64_t& stored,
                    std::string& err);
   bool set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std::string& err);
@@ -407,6 +417,7 @@ class Renderer {
   void free_scene();
   void free_paths();
   void free_photons();
+  bool upload_photons(const PhotonTree& tree, std::string& err);
   // Sample rounds, per screen half: as the reference's two RenderInstances
   // (wasm_interface.rs:90-94, :374-379), each half has its own strategy and
   // its own sequence of sample positions, and compute(n) advances the left

@@ -135,7 +135,6 @@ constexpr uint32_t kTreeFlag = 0x20000000u;
 #endif
 constexpr uint32_t kFlagBounced = 1u;   // has_diffuse_bounced
 constexpr uint32_t kTypeShift = 2u;     // render type (2 bits)
-constexpr uint32_t kOctLdsWords = 6144;  // PNEE octree words k_shade stages in LDS (24 KB per block)
 constexpr uint32_t kShadeLights = 16;    // light records k_shade stages in LDS (80 B each)
 constexpr uint32_t kDepthShift = 8u;    // bounce depth (10 bits: <= kMaxBounces)
 constexpr uint32_t kDepthMask = 0x3FFu;
@@ -1141,7 +1140,6 @@ __device__ __forceinline__ void oct_axis(float v, float lo, float hi, float& w, 
 // the cell [lo(k), lo(k+1)) holding w (clamped to the root box), from the
 // most significant down. A descent then needs no bound arithmetic: one child
 // read and a few integer operations per level.
-constexpr int kOctLattice = 20;
 #ifndef WPT_OCT_TABLE
 #define WPT_OCT_TABLE 1  // 0: the neighbour cells by walks only (A/B builds)
 #endif
@@ -1920,6 +1918,46 @@ struct WaveFeed {
     return p;
   }
 };
+
+// ---------------------------------------------------------------------------
+// Test hook (Renderer::photon_sample): photon_sample of n points, point i on
+// the xorshift32 state st_in[i], reading the octree as k_shade<.., PNEE, OCT>
+// does. The staging loop and the views are k_shade's, restated here so that
+// k_shade's own code does not change.
+// ---------------------------------------------------------------------------
+template <int OCT>
+__global__ void __launch_bounds__(kShadeBlock) k_photon_sample(DevScene S, uint32_t n, const float* __restrict__ pts,
+                                                               const uint32_t* __restrict__ st_in,
+                                                               uint32_t* __restrict__ light, float* __restrict__ pdf,
+                                                               uint32_t* __restrict__ st_out) {
+  extern __shared__ uint32_t s_oct[];
+  if (OCT != 0) {
+    const uint32_t nc = S.oct_nodes, nw = S.oct_lds_words;
+    for (uint32_t k = threadIdx.x; k < nw; k += kShadeBlock)
+      s_oct[k] = k < nc ? S.oct_child[k] : __float_as_uint(S.oct_cum[k - nc]);
+  }
+  __syncthreads();
+  using OV = std::conditional_t<OCT == 2, OctL2, std::conditional_t<OCT == 1, OctL1, OctG>>;
+  OV O;
+  if constexpr (OCT == 2) {
+    O.child = (const lds_u32*)s_oct;
+    O.cum = (const lds_f32*)(s_oct + S.oct_nodes);
+  } else if constexpr (OCT == 1) {
+    O.child = (const lds_u32*)s_oct;
+    O.cum = S.oct_cum;
+  } else {
+    O.child = S.oct_child;
+    O.cum = S.oct_cum;
+  }
+  for (uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x; i < n; i += gridDim.x * kShadeBlock) {
+    uint32_t s = st_in[i], li = 0;
+    float p = 0.0f;
+    photon_sample(S, O, s, mk(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]), li, p);
+    light[i] = li;
+    pdf[i] = p;
+    st_out[i] = s;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // PNEE preprocessing (RenderInstance::preprocess_photons, tracer.rs:126-152)
@@ -2964,7 +3002,8 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
       return true;
     case 27: if (!range(0, 100)) return false; async_grid_pct_ = (int)v; return true;
     case 28:
-    case 29: err = "read-only option"; return false;
+    case 29:
+    case 41: err = "read-only option"; return false;
     case 24:
       if (!range(1, kMaxLanes - kAsyncLane0 - 1)) return false;  // the fill lane follows them
       if (!drain_async(err)) return false;
@@ -3019,6 +3058,10 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     // scene; and whether its finite shapes are all triangles
     case 28: v = !scene_ok_ ? -1 : !ds_.use_bvh ? 2 : trav_ext_; return true;
     case 29: v = !scene_ok_ ? -1 : ds_.tri_only ? 1 : 0; return true;
+    // read-only: where k_shade's PNEE variants read the session's octree (the
+    // OCT of the launch): 0 global memory, 1 child array in LDS, 2 child
+    // array and CDFs in LDS; -1 no tree
+    case 41: v = !photons_ok_ ? -1 : ds_.oct_lds_words == 0 ? 0 : (ds_.oct_lds_words > ds_.oct_nodes ? 2 : 1); return true;
     case 24: v = stock_lanes_; return true;
     default: return false;
   }
@@ -5007,9 +5050,15 @@ bool Renderer::build_photons(std::string& err) {
       photons_shot_ += used;
     }
   }
-  photons_stored_ = tree.num_photons();
   stats_.photon_rays += photons_shot_;
-  stats_.photons += photons_stored_;
+  stats_.photons += tree.num_photons();
+  return upload_photons(tree, err);
+}
+
+// Freeze `tree` and upload it as the session's PNEE octree: the child array,
+// the CDFs, photon_sample's corner table and the words k_shade stages in LDS.
+bool Renderer::upload_photons(const PhotonTree& tree, std::string& err) {
+  photons_stored_ = tree.num_photons();
   tree.freeze(oct_child_, oct_cum_);
   HIP_OK(hipMalloc(&d_oct_child_, sizeof(uint32_t) * oct_child_.size()));
   HIP_OK(hipMemcpy(d_oct_child_, oct_child_.data(), sizeof(uint32_t) * oct_child_.size(), hipMemcpyHostToDevice));
@@ -5021,61 +5070,13 @@ bool Renderer::build_photons(std::string& err) {
   ds_.oct_cum = d_oct_cum_;
   ds_.oct_nodes = (uint32_t)oct_child_.size();
   {
-    // photon_sample's neighbour cells, per leaf and offset case (xo, yo, zo
-    // = -1 / +1 per axis: bits 2, 1, 0 of the case): the walks oct_walk does
-    // on the device, from the leaf's lattice index (depth <= kOctLattice)
-    const size_t nn = oct_child_.size();
-    std::vector<uint32_t> corners(64 * nn, 0u);
-    auto walk = [&](uint32_t ix, uint32_t iy, uint32_t iz, int d) {
-      uint32_t node = 0;
-      for (int l = d - 1; l >= 0; l--) {
-        const uint32_t c = oct_child_[node];
-        if (c == 0u) break;
-        node = c + (((ix >> l) & 1u) << 2) + (((iy >> l) & 1u) << 1) + ((iz >> l) & 1u);
-      }
-      return node;
-    };
-    struct Item {
-      uint32_t node;
-      int d;
-      uint32_t kx, ky, kz;
-    };
-    std::vector<Item> todo{{0u, 0, 0u, 0u, 0u}};
-    while (!todo.empty()) {
-      const Item it = todo.back();
-      todo.pop_back();
-      const uint32_t c0 = oct_child_[it.node];
-      if (c0 != 0u) {
-        if (it.d < kOctLattice)
-          for (uint32_t j = 0; j < 8; j++)
-            todo.push_back({c0 + j, it.d + 1, 2 * it.kx + ((j >> 2) & 1u), 2 * it.ky + ((j >> 1) & 1u),
-                            2 * it.kz + (j & 1u)});
-        continue;
-      }
-      const int64_t last = ((int64_t)1 << it.d) - 1;
-      auto adj = [&](uint32_t k, int off) {
-        const int64_t a = (int64_t)k + off;
-        return (uint32_t)(a < 0 ? 0 : (a > last ? last : a));
-      };
-      for (uint32_t oc = 0; oc < 8; oc++) {
-        const uint32_t ax = adj(it.kx, (oc & 4u) ? 1 : -1), ay = adj(it.ky, (oc & 2u) ? 1 : -1),
-                       az = adj(it.kz, (oc & 1u) ? 1 : -1);
-        uint32_t* row = corners.data() + 64 * (size_t)it.node + 8 * oc;
-        row[0] = it.node;
-        for (uint32_t c = 1; c < 8; c++)
-          row[c] = walk((c & 4u) ? ax : it.kx, (c & 2u) ? ay : it.ky, (c & 1u) ? az : it.kz, it.d);
-      }
-    }
+    std::vector<uint32_t> corners;
+    oct_corner_table(oct_child_, corners);
     HIP_OK(hipMalloc(&d_oct_corners_, sizeof(uint32_t) * corners.size()));
     HIP_OK(hipMemcpy(d_oct_corners_, corners.data(), sizeof(uint32_t) * corners.size(), hipMemcpyHostToDevice));
     ds_.oct_corners = d_oct_corners_;
   }
-  {
-    // k_shade's LDS copy of the tree (dynamic shared memory, 6 blocks per CU
-    // must still fit): child and CDFs, else the child array alone, else none
-    const size_t nodes = oct_child_.size(), all = nodes + oct_cum_.size();
-    ds_.oct_lds_words = all <= kOctLdsWords ? (uint32_t)all : nodes <= kOctLdsWords ? (uint32_t)nodes : 0u;
-  }
+  ds_.oct_lds_words = oct_lds_words(oct_child_.size(), oct_cum_.size());
   photons_ok_ = true;
   return true;
 }
@@ -5089,6 +5090,66 @@ bool Renderer::photon_tree(std::vector<uint32_t>& child, std::vector<float>& cum
   shot = photons_shot_;
   stored = photons_stored_;
   return true;
+}
+
+int Renderer::install_photons(size_t n, const uint32_t* light, const float* loc3, const float* intensity,
+                              std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return 0; }
+  for (size_t i = 0; i < n; i++)
+    if (light[i] >= ds_.num_lights) { err = "photon light id out of range"; return -1; }
+  if (!drain_async(err)) return 0;  // async batches read the tree freed below
+  HIP_OK(hipStreamSynchronize(stream_));
+  free_photons();
+  PhotonTree tree(ds_.num_lights);
+  for (size_t i = 0; i < n; i++) tree.insert(light[i], mk(loc3[3 * i], loc3[3 * i + 1], loc3[3 * i + 2]), intensity[i]);
+  photons_shot_ = 0;
+  return upload_photons(tree, err) ? 1 : 0;
+}
+
+int Renderer::photon_sample(size_t n, const float* pts3, const uint32_t* states, int view, bool table, uint32_t* light,
+                            float* pdf, uint32_t* states_out, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return 0; }
+  if (ds_.num_lights == 0) { err = "photon_sample: the scene has no lights"; return -1; }
+  if (n > 0xFFFFFFFFull / 16) { err = "too many points"; return -1; }
+  if (!build_photons(err)) return 0;
+  DevScene S = ds_;
+  const size_t nodes = oct_child_.size(), all = nodes + oct_cum_.size();
+  if (view == 2 && all <= kOctLdsWords) S.oct_lds_words = (uint32_t)all;
+  else if (view == 1 && nodes <= kOctLdsWords) S.oct_lds_words = (uint32_t)nodes;
+  else if (view == 0) S.oct_lds_words = 0;
+  else { err = "photon_sample: the tree does not fit this view"; return -1; }
+  if (!table) S.oct_corners = nullptr;
+  if (n == 0) return 1;
+  float* dp = nullptr;
+  uint32_t* ds = nullptr;
+  uint32_t* dl = nullptr;
+  float* df = nullptr;
+  uint32_t* dso = nullptr;
+  bool ok = hipMalloc(&dp, 12 * n) == hipSuccess && hipMalloc(&ds, 4 * n) == hipSuccess &&
+            hipMalloc(&dl, 4 * n) == hipSuccess && hipMalloc(&df, 4 * n) == hipSuccess &&
+            hipMalloc(&dso, 4 * n) == hipSuccess;
+  if (ok)
+    ok = hipMemcpyAsync(dp, pts3, 12 * n, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+         hipMemcpyAsync(ds, states, 4 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
+  if (ok) {
+    const uint32_t nn = (uint32_t)n, grid = (nn + kShadeBlock - 1) / kShadeBlock;
+    const size_t smem = 4 * (size_t)S.oct_lds_words;
+    if (view == 2) k_photon_sample<2><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
+    else if (view == 1) k_photon_sample<1><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
+    else k_photon_sample<0><<<grid, kShadeBlock, 0, stream_>>>(S, nn, dp, ds, dl, df, dso);
+    ok = hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(light, dl, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(pdf, df, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipMemcpyAsync(states_out, dso, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+         hipStreamSynchronize(stream_) == hipSuccess;
+  }
+  (void)hipFree(dp);
+  (void)hipFree(ds);
+  (void)hipFree(dl);
+  (void)hipFree(df);
+  (void)hipFree(dso);
+  if (!ok) err = "HIP error in photon_sample";
+  return ok ? 1 : 0;
 }
 
 bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err) {

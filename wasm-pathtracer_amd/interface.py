@@ -175,6 +175,53 @@ def photon_tree(num_lights):
     return child, cum[: n * num_lights].reshape(n, num_lights), int(ss[0]), int(ss[1])
 
 
+def _photon_arrays(photons):
+    light, loc, intensity = photons
+    li = np.ascontiguousarray(light, dtype=np.uint32)
+    lo = np.ascontiguousarray(loc, dtype=np.float32).reshape(-1, 3)
+    it = np.ascontiguousarray(intensity, dtype=np.float32)
+    assert li.shape[0] == lo.shape[0] == it.shape[0]
+    return li, lo, it
+
+
+def photon_build(num_lights, photons):
+    """Host-only: the frozen octree of a photon list (light ids, locations
+    (n, 3), intensities; insertion order): (child[nodes], cum[nodes,
+    num_lights], corners[nodes, 8, 8]) (wpt_photon_build)."""
+    li, lo, it = _photon_arrays(photons)
+    L = lib()
+    args = (num_lights, li.shape[0], li.ctypes.data, lo.ctypes.data, it.ctypes.data)
+    n = _check(L.wpt_photon_build(*args, None, None, None))
+    child = np.empty(n, dtype=np.uint32)
+    cum = np.empty(n * max(num_lights, 1), dtype=np.float32)
+    corners = np.empty((n, 8, 8), dtype=np.uint32)
+    _check(L.wpt_photon_build(*args, child.ctypes.data, cum.ctypes.data, corners.ctypes.data))
+    return child, cum[: n * num_lights].reshape(n, num_lights), corners
+
+
+def install_photons(photons):
+    """Test hook: the photon list as the session's PNEE octree, until a new
+    scene or frame seed drops it (wpt_install_photons)."""
+    li, lo, it = _photon_arrays(photons)
+    _check(lib().wpt_install_photons(li.shape[0], li.ctypes.data, lo.ctypes.data, it.ctypes.data))
+
+
+def photon_sample(points, states, view, table=True):
+    """Test hook: the device's PhotonTree::sample of points (n, 3), point i on
+    the xorshift32 state states[i], reading the octree as the shade kernel's
+    variant `view` (0, 1, 2) does: (light, pdf, state after) per point."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    s = np.ascontiguousarray(states, dtype=np.uint32)
+    n = p.shape[0]
+    assert s.shape == (n,)
+    light = np.empty(n, dtype=np.uint32)
+    pdf = np.empty(n, dtype=np.float32)
+    out = np.empty(n, dtype=np.uint32)
+    _check(lib().wpt_photon_sample(n, p.ctypes.data, s.ctypes.data, int(view), 1 if table else 0, light.ctypes.data,
+                                   pdf.ctypes.data, out.ctypes.data))
+    return light, pdf, out
+
+
 def read_radiance(width, height):
     acc = np.empty(width * height * 3, dtype=np.float32)
     cnt = np.empty(width * height, dtype=np.uint32)
@@ -272,7 +319,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "fill": 25, "async_prio": 26, "async_grid_pct": 27, "scene_traversal": 28, "scene_tri_only": 29,
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
-           "presolve_shadow": 39, "gen_shade": 40}
+           "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
