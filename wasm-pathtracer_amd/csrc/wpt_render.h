@@ -379,6 +379,7 @@ class Renderer {
                  uint32_t part_n = 0, const Batch* map = nullptr);
   // the Batch state machine: lanes and generate; bounces until done or a
   // live-count read is pending (block: wait for it); the tail
+  auto shade_params() const;  // the ShadeParams of a batch's shade kernels (wpt_render.hip)
   bool batch_begin(Batch& B, std::string& err);
   bool batch_advance(Batch& B, bool block, std::string& err);
   bool batch_tail(Batch& B, std::string& err);

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <thread>
@@ -908,10 +909,106 @@ __device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* 
   return g;
 }
 
+// Where path g's radiance is accumulated (pix_out): its pixel, or the entry of
+// a sample round's list (rnd_off); a stock batch (stock_slots != 0) writes the
+// path's stock slot, pixel x slots + sample mod slots, instead.
+__device__ __forceinline__ uint32_t path_slot(const GenPath& g, const uint32_t* rnd_off, uint32_t stock_slots) {
+  return stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+}
+
+// A miss of a path with throughput thr adds nothing to its colour: throughput *
+// background (tracer.rs:325-327) is +0 in every component (black background,
+// finite throughput). The sum is then the colour itself (colours are sums of
+// non-negative terms from +0, never -0), so shade_path's miss branch skips the
+// read-modify-write, and a producer that resolves a ray to a miss may drop it
+// (drop-miss): exact, because both evaluate this one expression on the same
+// operands, the throughput stored with the ray.
+__device__ __forceinline__ bool adds_nothing(V3 thr, const DevScene& S) {
+  const V3 add_c = mulv(thr, mk(S.bg[0], S.bg[1], S.bg[2]));
+  return (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+}
+
+// A scan column of BlockAppend that carries several counts of a block of PATHS
+// paths: BITS-bit fields, field k at bit k * BITS. Every field is at most PATHS
+// over the block, so the packed sums do not carry into the next field.
+template <uint32_t BITS, uint32_t PATHS>
+struct Fields {
+  static_assert(PATHS < (1u << BITS), "a block's counts share a word");
+  static constexpr uint32_t kMask = (1u << BITS) - 1u;
+  static __device__ __forceinline__ uint32_t pack(uint32_t a, uint32_t b) { return a | (b << BITS); }
+  static __device__ __forceinline__ uint32_t pack(uint32_t a, uint32_t b, uint32_t c) {
+    return a | (b << BITS) | (c << (2 * BITS));
+  }
+  static __device__ __forceinline__ uint32_t get(uint32_t x, uint32_t k) { return (x >> (k * BITS)) & kMask; }
+  // the highest field in use (nothing above it)
+  static __device__ __forceinline__ uint32_t top(uint32_t x, uint32_t k) { return x >> (k * BITS); }
+};
+// k_shade: next rays resolved, dropped, shadow rays resolved;
+// k_generate_shade besides: primaries dropped, shaded
+using ShadeFields = Fields<10, kShadeBlock>;
+
+// Block append: the waves of a block count what their lanes add to each of N
+// output ranges (a column per range; a column may hold several counts as
+// Fields), one block-wide scan gives every wave its offset within the block,
+// and ONE atomic instruction reserves the block's share of every range: the
+// lanes from COLS - 1 on of wave 0 each add to a 64-bit counter of their own.
+// s_off[c][w]: wave w's count in column c, then (after reserve) the range
+// entry its first lane writes. COLS: the block's waves (times k_generate_ps's tiles).
+using u64 = unsigned long long;
+template <uint32_t N, uint32_t COLS>
+struct BlockAppend {
+  static constexpr uint32_t kCols = COLS;
+  uint32_t (&s_off)[N][COLS];
+  // What a lane of wave 0 adds, and whether it takes part.
+  struct Take { u64* ctr; u64 inc; bool go; };
+  static __device__ __forceinline__ Take take(void* slot, uint32_t lo, uint32_t hi, bool go) {
+    return Take{static_cast<u64*>(slot), (u64)lo | ((u64)hi << 32), go};
+  }
+  // Where column c's base comes back from: the low or high word of what lane
+  // COLS - 1 + lane got (lane < 0: the column is only counted); mask: the
+  // field of a Fields column that is a range's count.
+  struct From { int lane; bool high; uint32_t mask; };
+  // lane 0 of a wave: its counts, to entry w of every column
+  __device__ __forceinline__ void publish(uint32_t w, const uint32_t (&cnt)[N]) const {
+    for (uint32_t c = 0; c < N; c++) s_off[c][w] = cnt[c];
+  }
+  // a column's total over the block, from its inclusive sum (which lane
+  // COLS - 1 holds itself)
+  static __device__ __forceinline__ uint32_t total(uint32_t incl) {
+    return (uint32_t)__shfl((int)incl, (int)(COLS - 1), 64);
+  }
+  // Wave 0, between two __syncthreads(): scans the columns, lets pick(incl)
+  // name each lane's counter and increment from the inclusive sums, and
+  // replaces the counts with the waves' first entries.
+  template <class F>
+  __device__ __forceinline__ void reserve(uint32_t lane, const From (&from)[N], F&& pick) const {
+    static_assert(COLS + N < 64, "the scan's totals and the other atomic lanes sit in one wave");
+    uint32_t own[N], incl[N];
+    for (uint32_t c = 0; c < N; c++) incl[c] = own[c] = lane < COLS ? s_off[c][lane] : 0u;
+    for (uint32_t q = 1; q < COLS; q <<= 1) {
+      uint32_t y[N];
+      for (uint32_t c = 0; c < N; c++) y[c] = __shfl_up(incl[c], q, 64);
+      for (uint32_t c = 0; c < N; c++) incl[c] += lane >= q ? y[c] : 0u;
+    }
+    const Take t = pick(incl);
+    u64 got = 0ull;
+    if (t.go) got = atomicAdd(t.ctr, t.inc);
+    uint32_t base[N];
+    for (uint32_t c = 0; c < N; c++)
+      base[c] = from[c].lane < 0 ? 0u
+                                 : (uint32_t)__shfl((int)(uint32_t)(from[c].high ? got >> 32 : got),
+                                                    (int)(COLS - 1) + from[c].lane, 64);
+    if (lane < COLS) {
+      for (uint32_t c = 0; c < N; c++)
+        if (from[c].lane >= 0) s_off[c][lane] = base[c] + ((incl[c] - own[c]) & from[c].mask);
+    }
+  }
+  // the range entry of the lane whose rank among the wave's writers is `rank`
+  __device__ __forceinline__ uint32_t at(uint32_t c, uint32_t w, uint32_t rank) const { return s_off[c][w] + rank; }
+};
+
 // Writes the batch's bounce-0 ray stream (path i at i): the kernel of batches
 // that presolve nothing (RR-only, no BVH, WPT_OPT_PRESOLVE = 0).
-// A stock batch (stock_slots != 0) writes the path's stock slot, pixel x
-// slots + sample mod slots, instead of its pixel.
 __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t* __restrict__ part_pix, uint64_t k0,
                                                      uint32_t n, uint32_t* __restrict__ pix_out,
                                                      float4* __restrict__ thr,
@@ -924,7 +1021,7 @@ __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t
   if (i == 0) *count0 = n;
   if (i >= n) return;
   const GenPath g = gen_path(P, part_pix, k0 + i, rnd_off, rnd_base, rnd_list);
-  pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+  pix_out[i] = path_slot(g, rnd_off, stock_slots);
   thr[i] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(g.type << kTypeShift));
   col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   ro[i] = make_float4(P.cam[0], P.cam[1], P.cam[2], __uint_as_float(g.s));  // w: the path's rng state
@@ -948,8 +1045,7 @@ __global__ void __launch_bounds__(kBlock) k_generate(GenParams P, const uint32_t
 // counters were the cause), but the 4-lane step, where the kernel runs under
 // the other lanes' traversal, gained nothing (profiles/dropmiss/README.md).
 // A primary ray resolved to a miss is dropped (drop_miss, WPT_OPT_DROP_MISS)
-// when throughput (1) * S.bg is +0 in every component, the product k_shade's
-// miss branch would test: the path keeps only pix_out and col (with
+// when its throughput (1) adds nothing: the path keeps only pix_out and col (with
 // stock_slots, the count word of a path that ended after one extension ray),
 // and the ray is counted in the high word of res0 by the same atomic.
 #ifndef WPT_GEN_TILE
@@ -968,16 +1064,14 @@ __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint3
                                                         int32_t* __restrict__ id_out, uint32_t* __restrict__ res0,
                                                         uint32_t drop_miss) {
   constexpr uint32_t kWaves = kBlock / 64, kCols = kGenTile * kWaves;
-  static_assert(kCols < 64, "the scan's totals and the second atomic lane sit in one wave");
-  static_assert(kBlock * kGenTile < 65536u, "a block's resolved and dropped counts share a word");
+  using F = Fields<16, kBlock * kGenTile>;  // column 1: resolved and stored, dropped
   __shared__ uint32_t s_off[2][kCols];
+  const BlockAppend<2, kCols> A{s_off};
   const uint32_t base = blockIdx.x * (kBlock * kGenTile);
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t below = (1ull << lane) - 1ull;
   const V3 cam = mk(P.cam[0], P.cam[1], P.cam[2]);
-  const V3 add_c = mulv(mk(1.0f, 1.0f, 1.0f), mk(S.bg[0], S.bg[1], S.bg[2]));  // shade_path's miss branch
-  const bool adds_nothing =
-      drop_miss != 0u && (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+  const bool drop_misses = drop_miss != 0u && adds_nothing(mk(1.0f, 1.0f, 1.0f), S);
   V3 dir[kGenTile];
   uint32_t rng[kGenTile], type[kGenTile];
   float pt[kGenTile];
@@ -993,11 +1087,11 @@ __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint3
     float t = 0.0f;
     int32_t id = -1;
     const bool res = valid && presolve_ray(S, *S.pre, cam, g.v, t, id);
-    const bool drop = res && id < 0 && adds_nothing;
+    const bool drop = res && id < 0 && drop_misses;
     pt[j] = t;
     pid[j] = id;
     if (valid) {
-      pix_out[i] = stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+      pix_out[i] = path_slot(g, rnd_off, stock_slots);
       // a dropped path of a stock batch ended after one extension ray and no shadow ray
       col[i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(stock_slots && drop ? 1u : 0u));
     }
@@ -1007,34 +1101,19 @@ __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint3
     hm[j] = __ballot(valid && !res);
     rm[j] = __ballot(res && !drop);
     const uint64_t dm = __ballot(drop);
-    if (lane == 0) {
-      s_off[0][j * kWaves + wid] = (uint32_t)__popcll(hm[j]);
-      s_off[1][j * kWaves + wid] = (uint32_t)__popcll(rm[j]) | ((uint32_t)__popcll(dm) << 16);
-    }
+    if (lane == 0)
+      A.publish(j * kWaves + wid,
+                {(uint32_t)__popcll(hm[j]), F::pack((uint32_t)__popcll(rm[j]), (uint32_t)__popcll(dm))});
   }
   __syncthreads();
   if (wid == 0) {
-    const uint32_t a = lane < kCols ? s_off[0][lane] : 0u, b = lane < kCols ? s_off[1][lane] : 0u;
-    uint32_t ia = a, ib = b;
-#pragma unroll
-    for (uint32_t q = 1; q < kCols; q <<= 1) {
-      const uint32_t ya = __shfl_up(ia, q, 64), yb = __shfl_up(ib, q, 64);
-      if (lane >= q) { ia += ya; ib += yb; }
-    }
-    // lane kCols - 1 holds both totals; lane kCols adds the second one
-    // (resolved and stored in the low word, dropped in the high word)
-    const uint32_t tb = (uint32_t)__shfl((int)ib, (int)(kCols - 1), 64);
-    unsigned long long got = 0ull;
-    if (lane == kCols - 1 || lane == kCols)
-      got = atomicAdd(reinterpret_cast<unsigned long long*>(lane == kCols - 1 ? count0 : res0),
-                      lane == kCols - 1 ? (unsigned long long)ia
-                                        : ((unsigned long long)(tb & 0xffffu) | ((unsigned long long)(tb >> 16) << 32)));
-    const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)got, (int)(kCols - 1), 64);
-    const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)got, (int)kCols, 64);
-    if (lane < kCols) {
-      s_off[0][lane] = ba + ia - a;
-      s_off[1][lane] = bb + ((ib - b) & 0xffffu);
-    }
+    // lane kCols - 1: the unresolved rays to count0; lane kCols: resolved and stored | dropped to res0
+    A.reserve(lane, {{0, false, ~0u}, {1, false, F::kMask}}, [&](const uint32_t(&incl)[2]) {
+      const uint32_t tb = A.total(incl[1]);
+      const bool first = lane == kCols - 1;
+      return A.take(first ? count0 : res0, first ? incl[0] : F::get(tb, 0), first ? 0u : F::top(tb, 1),
+                    first || lane == kCols);
+    });
   }
   __syncthreads();
 #pragma unroll
@@ -1044,11 +1123,11 @@ __global__ void __launch_bounds__(kBlock) k_generate_ps(GenParams P, const uint3
     const uint32_t i = base + j * kBlock + threadIdx.x;
     uint32_t p;  // the ray's entry in the stream
     if (back) {
-      p = n - 1u - (s_off[1][j * kWaves + wid] + (uint32_t)__popcll(rm[j] & below));
+      p = n - 1u - A.at(1, j * kWaves + wid, (uint32_t)__popcll(rm[j] & below));
       t_out[p] = pt[j];
       id_out[p] = pid[j];
     } else {
-      p = s_off[0][j * kWaves + wid] + (uint32_t)__popcll(hm[j] & below);
+      p = A.at(0, j * kWaves + wid, (uint32_t)__popcll(hm[j] & below));
     }
     thr[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(type[j] << kTypeShift));
     ro[p] = make_float4(cam.x, cam.y, cam.z, __uint_as_float(rng[j]));             // w: the path's rng state
@@ -1086,6 +1165,28 @@ struct OctViewT {
 using OctG = OctViewT<const uint32_t*, const float*>;
 using OctL1 = OctViewT<const lds_u32*, const float*>;
 using OctL2 = OctViewT<const lds_u32*, const lds_f32*>;
+// The view a kernel's OCT parameter selects: 0 global memory, 1 the child
+// array from LDS, 2 child array and CDFs from LDS. For 1 and 2 the block
+// copies the frozen octree (child, then the CDFs) into s_oct, the dynamic
+// shared memory the launch gave (S.oct_lds_words; the per-level descents of
+// photon_sample are chains of dependent loads). The caller's __syncthreads()
+// comes before the first read through the view.
+template <int OCT>
+using OctView = std::conditional_t<OCT == 2, OctL2, std::conditional_t<OCT == 1, OctL1, OctG>>;
+template <int OCT>
+__device__ __forceinline__ OctView<OCT> oct_view(const DevScene& S, uint32_t* s_oct) {
+  if (OCT != 0) {
+    const uint32_t nc = S.oct_nodes, nw = S.oct_lds_words;
+    for (uint32_t k = threadIdx.x; k < nw; k += kShadeBlock)
+      s_oct[k] = k < nc ? S.oct_child[k] : __float_as_uint(S.oct_cum[k - nc]);
+  }
+  OctView<OCT> O;
+  if constexpr (OCT != 0) O.child = (const lds_u32*)s_oct;
+  else O.child = S.oct_child;
+  if constexpr (OCT == 2) O.cum = (const lds_f32*)(s_oct + S.oct_nodes);
+  else O.cum = S.oct_cum;
+  return O;
+}
 
 template <class OV>
 __device__ uint32_t oct_find(const DevScene& S, const OV& O, V3 v, int max_depth, float b[6], int& depth) {
@@ -1333,14 +1434,11 @@ __device__ __forceinline__ void shade_path(const DevScene& S, const OV& O, const
     if constexpr (CR) reinterpret_cast<uint32_t*>(col + path)[3] = depth | (nsh << 16);
   };
   if (id < 0) {
-    // miss: color += throughput * background (tracer.rs:325-327). When the
-    // product is +0 in every component (black background, finite throughput)
-    // the sum is the colour itself (colours are sums of non-negative terms
-    // from +0, never -0), so the read-modify-write is skipped.
-    const V3 add_c = mulv(thr, mk(S.bg[0], S.bg[1], S.bg[2]));
-    if ((__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) != 0u) {
+    // miss: color += throughput * background (tracer.rs:325-327), a
+    // read-modify-write that is skipped when it adds nothing
+    if (!adds_nothing(thr, S)) {
       const float4 c4 = col[path];
-      const V3 c = add(ld3(c4), add_c);
+      const V3 c = add(ld3(c4), mulv(thr, mk(S.bg[0], S.bg[1], S.bg[2])));
       col[path] = make_float4(c.x, c.y, c.z, c4.w);
     }
     end_counts(flags >> kShadowShift);
@@ -1469,6 +1567,137 @@ __device__ __forceinline__ void add_contribution_xyz(float4* __restrict__ col, f
   p[2] = z;
 }
 
+// The light records (5 float4 each) into the block's LDS when they fit (at most
+// kShadeLights; returns that): the NEE light pick is then an LDS read (shade_path's
+// lq) instead of a dependent global round trip. The caller's __syncthreads() follows.
+__device__ __forceinline__ bool stage_lights(const DevScene& S, f4v (&s_light)[5 * kShadeLights]) {
+  const bool lds_lights = S.num_lights <= kShadeLights;
+  if (lds_lights) {
+    for (uint32_t k = threadIdx.x; k < 5 * S.num_lights; k += kShadeBlock) {
+      const float4 v = S.lights[k];
+      s_light[k] = f4v{v.x, v.y, v.z, v.w};
+    }
+  }
+  return lds_lights;
+}
+
+// The tail of the presolving producers (k_shade<.., PS = true>, k_generate_shade): what
+// presolve_out decides about a shaded path's rays; count_out, shade_take, store_out append them.
+struct Verdict {
+  bool alive;  // the path goes on and its next ray is stored
+  bool res;    // stored resolved: at the back of the next stream, with (t, id)
+  bool drop;   // the next ray is resolved to a miss that adds nothing: to neither end
+  bool sres;   // the shadow ray ends unoccluded: added to col here
+  float t;  // with res: the ray's hit record
+  int32_t id;
+};
+// A survivor's next ray is presolved. One resolved to a miss is dropped
+// (P.drop_miss) when it adds nothing: the next shade_path would test that on
+// the same operands before it returns, so nothing reads the record; with CR
+// the path gets the count word the next bounce's end_counts would have written.
+// The shadow ray: one that provably ends unoccluded (presolve_shadow,
+// wpt_presolve.h; P.presolve_shadow) adds its contribution in this launch,
+// the read-modify-write k_shadow would do (store_out), and takes no slot of
+// the shadow stream. The path's additions keep their order: shade_path adds
+// nothing to col for a path that emits a shadow ray, and this launch runs
+// after the traversal of the previous bounce's shadow rays. (After a CR path's
+// count word.) SHADOW = false: the PNEE variant that reads the octree from
+// global memory; with the shadow presolve it needs 24 B of scratch, not 20.
+template <bool SHADOW, bool CR>
+__device__ __forceinline__ Verdict presolve_out(const DevScene& S, const ShadeParams& P, float4* __restrict__ col,
+                                                const ShadeOut R) {
+  bool alive = R.alive, res = false;
+  float pt = 0.0f;
+  int32_t pid = -1;
+  if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
+  bool drop = false;
+  if (res && pid < 0 && P.drop_miss) drop = adds_nothing(ld3(R.th), S);
+  if (drop) {
+    alive = res = false;
+    if constexpr (CR) {
+      const uint32_t f = __float_as_uint(R.th.w);
+      reinterpret_cast<uint32_t*>(col + __float_as_uint(R.rd.w))[3] =
+          (((f >> kDepthShift) & kDepthMask) + 1u) | ((f >> kShadowShift) << 16);
+    }
+  }
+  bool sres = false;
+  if constexpr (SHADOW) {
+    if (R.shadow && P.presolve_shadow)
+      sres = presolve_shadow(S, *S.pre, ld3(R.so), ld3(R.sd), R.so.w, (int32_t)__float_as_uint(R.sd.w));
+  }
+  return Verdict{alive, res, drop, sres, pt, pid};
+}
+
+// The wave's lanes per output range: the next ray to the front of the next
+// stream, the shadow ray to the shadow stream, the next ray to the back. Their
+// counts to cnt[0..1]; with PS cnt[2]: next rays resolved, dropped, shadow rays resolved.
+struct OutMasks { uint64_t am, sm, rm; };
+template <bool PS>
+__device__ __forceinline__ OutMasks count_out(const ShadeOut R, const Verdict V, uint32_t* cnt) {
+  const uint64_t am = __ballot(V.alive && !V.res), sm = __ballot(R.shadow && !V.sres), rm = PS ? __ballot(V.res) : 0ull;
+  cnt[0] = (uint32_t)__popcll(am);
+  cnt[1] = (uint32_t)__popcll(sm);
+  if constexpr (PS)
+    cnt[2] = ShadeFields::pack((uint32_t)__popcll(rm), (uint32_t)__popcll(__ballot(V.drop)),
+                               (uint32_t)__popcll(__ballot(V.sres)));
+  return OutMasks{am, sm, rm};
+}
+
+// The counters of those three columns, for lanes W - 1 .. W + 1 of wave 0
+// (W = BA's COLS): the bounce's append counter (ia survivors | ib streamed
+// shadow rays), the next bounce's presolved slot, which is kResWord words past
+// `append` (wpt_render.h; resolved | dropped), and the bounce's slot of the
+// block after the presolved counts (kShResWord), kShResWord - 2 words past it
+// (the shadow rays resolved here). tc: the third column's total.
+// The distances are made here: as a plain constant the compiler keeps one in
+// a VGPR across the kernel's whole loop (shade_path's peak).
+template <class BA>
+__device__ __forceinline__ typename BA::Take shade_take(uint32_t lane, u64* append, uint32_t ia, uint32_t ib,
+                                                        uint32_t tc) {
+  constexpr uint32_t W = BA::kCols;
+  uint32_t off;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)(kResWord / 2)));
+  if (lane == W + 1) asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)((kShResWord - 2) / 2)));
+  u64 inc = (u64)ia | ((u64)ib << 32);
+  if (lane == W) inc = (u64)ShadeFields::get(tc, 0) | ((u64)ShadeFields::get(tc, 1) << 32);
+  if (lane == W + 1) inc = (u64)ShadeFields::top(tc, 2);
+  return typename BA::Take{append + (lane == W - 1 ? 0u : off), inc, lane >= W - 1 && lane <= W + 1};
+}
+
+// After the reserve: a survivor's next ray to the front or, resolved, to the
+// back of the next stream (entries end - 1 downward) with its record (t_nx,
+// id_nx); the shadow ray to col or to the shadow stream. C0: BA's first of
+// the three columns.
+template <bool PS, uint32_t C0, class BA>
+__device__ __forceinline__ void store_out(const BA& A, uint32_t wid, uint64_t below, const OutMasks M, const ShadeOut R,
+                                          const Verdict V, const RayStream& out, const ShadowStream& sh,
+                                          float4* __restrict__ col, float* __restrict__ t_nx,
+                                          int32_t* __restrict__ id_nx, uint32_t end) {
+  if (V.alive) {
+    uint32_t p = A.at(C0, wid, (uint32_t)__popcll(M.am & below));
+    if constexpr (PS) {
+      if (V.res) p = end - 1u - A.at(C0 + 2, wid, (uint32_t)__popcll(M.rm & below));
+    }
+    st_stream(out.o + p, R.ro);
+    st_stream(out.d + p, R.rd);
+    st_stream(out.thr + p, R.th);
+    if constexpr (PS) {
+      if (V.res) {
+        t_nx[p] = V.t;
+        id_nx[p] = V.id;
+      }
+    }
+  }
+  if (V.sres) {
+    add_contribution_xyz(col, R.sc);
+  } else if (R.shadow) {
+    const uint32_t p = A.at(C0 + 1, wid, (uint32_t)__popcll(M.sm & below));
+    st_stream(sh.o + p, R.so);
+    st_stream(sh.d + p, R.sd);
+    st_stream(sh.c + p, R.sc);
+  }
+}
+
 // Shade kernel: one bounce of the path loop for paths 0..n-1 of the input
 // stream. A block shades kShadeBlock (256) consecutive paths, then appends the survivors
 // and the shadow rays in path order: one block-wide scan of the two flags and
@@ -1483,25 +1712,18 @@ __device__ __forceinline__ void add_contribution_xyz(float4* __restrict__ col, f
 // With PS the streams are two-ended (wpt_presolve.h): entries 0..nh-1
 // (count) are the rays the traversal kernel traced, the nr entries from end-1
 // downward (res_in) the rays their producer resolved, hit records beside both.
-// A survivor's next ray is presolved here; resolved ones are appended to the
-// back of the next stream with their record (t_nx, id_nx: the other pair of
-// hit-record buffers, since this launch still reads t_in / id_in). The third
-// count is reserved in the same scan; its atomic is the same instruction as
-// the append counter's: lanes kWaves-1 and kWaves, two addresses.
-// A ray resolved to a miss is dropped (P.drop_miss) when throughput * S.bg is
-// +0 in every component: that is the product, on the same operands, the next
-// shade_path would test before it returns, so nothing reads the record. A
-// dropped ray goes to neither end of the next stream and is counted in the
-// high word of the presolved slot (the scan carries three 10-bit fields per
-// wave, resolved | dropped << 10 | resolved shadow rays << 20, at most 256 each
-// over the block, so the same column and the same atomic serve);
-// with CR it writes the count word the next bounce's end_counts would have.
-// A shadow ray that presolve_shadow resolves (P.presolve_shadow) is added to
-// col here and written to no stream; it is counted in the bounce's slot at
-// kShResWord by a third lane of the same atomic. The append counter's high
-// word, which k_shadow / k_trace read, counts the streamed shadow rays only.
-// OCT (PNEE): where photon_sample reads the octree: 0 global memory, 1 the
-// child array from LDS, 2 child array and CDFs from LDS (oct_lds_words).
+// What a path emits is decided here (presolve_out): a resolved next ray is
+// appended to the back of the next stream with its record (t_nx, id_nx: the
+// other pair of hit-record buffers, since this launch still reads t_in /
+// id_in), a dropped one goes to neither end, a resolved shadow ray is added to
+// col and written to no stream. The scan's third column carries their three
+// counts (ShadeFields), and their atomics are the same instruction as the
+// append counter's (shade_take): lane kWaves adds the resolved and the dropped
+// rays to the low and high word of the next bounce's presolved slot, lane
+// kWaves + 1 the resolved shadow rays to the bounce's slot at kShResWord. The
+// append counter's high word, which k_shadow / k_trace read, counts the
+// streamed shadow rays only.
+// OCT (PNEE): where photon_sample reads the octree (oct_view).
 template <bool TRI_ONLY, bool PNEE, int OCT, bool CR = false, bool PS = false>
 __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in, RayStream out,
                                                        ShadowStream sh, float4* __restrict__ col,
@@ -1511,49 +1733,26 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
                                                        float* __restrict__ t_nx, int32_t* __restrict__ id_nx,
                                                        uint32_t end) {
   constexpr uint32_t kWaves = kShadeBlock / 64;
-  static_assert(kWaves + 1 < 64, "the scan's totals and the other atomic lanes sit in one wave");
-  static_assert(kShadeBlock < 1024, "three 10-bit fields in the scan's third column");
+  using BA = BlockAppend<PS ? 3 : 2, kWaves>;
   __shared__ uint32_t s_off[PS ? 3 : 2][kWaves];
   __shared__ f4v s_light[5 * kShadeLights];
+  const BA A{s_off};
   const uint32_t nh = *count;
   // the presolved counts sit at fixed distances from the append counter
   // (kResWord, wpt_render.h): this bounce's 2 words before the slot of the
   // next bounce's, which is kResWord words past `append` (no further
   // arguments: the NEE variant's scalar registers are all in use)
   const uint32_t n = PS ? nh + reinterpret_cast<const uint32_t*>(append)[kResWord - 2] : nh;
-  // the light records (5 float4 each) into LDS when they fit: the NEE light
-  // pick is then an LDS read instead of a dependent global round trip
-  const bool lds_lights = S.num_lights <= kShadeLights;
-  if (lds_lights) {
-    for (uint32_t k = threadIdx.x; k < 5 * S.num_lights; k += kShadeBlock) {
-      const float4 v = S.lights[k];
-      s_light[k] = f4v{v.x, v.y, v.z, v.w};
-    }
-  }
-  // PNEE: the frozen octree (child, then the CDFs) into LDS when it fits the
-  // dynamic shared memory the launch gave (oct_lds_words; the per-level
-  // descents of photon_sample are chains of dependent loads)
+  const bool lds_lights = stage_lights(S, s_light);
   extern __shared__ uint32_t s_oct[];
-  if (PNEE && OCT != 0) {
-    const uint32_t nc = S.oct_nodes, nw = S.oct_lds_words;
-    for (uint32_t k = threadIdx.x; k < nw; k += kShadeBlock)
-      s_oct[k] = k < nc ? S.oct_child[k] : __float_as_uint(S.oct_cum[k - nc]);
-  }
+  using OV = OctView<PNEE ? OCT : 0>;
+  const OV O = oct_view<PNEE ? OCT : 0>(S, s_oct);
   __syncthreads();  // the light records and the octree
-  using OV = std::conditional_t<OCT == 2, OctL2, std::conditional_t<OCT == 1, OctL1, OctG>>;
-  OV O;
-  if constexpr (OCT == 2) {
-    O.child = (const lds_u32*)s_oct;
-    O.cum = (const lds_f32*)(s_oct + S.oct_nodes);
-  } else if constexpr (OCT == 1) {
-    O.child = (const lds_u32*)s_oct;
-    O.cum = S.oct_cum;
-  } else {
-    O.child = S.oct_child;
-    O.cum = S.oct_cum;
-  }
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t below = (1ull << lane) - 1ull;
+  // the columns' bases: both words of what lane kWaves - 1 got, the low word of lane kWaves
+  typename BA::From from[PS ? 3 : 2] = {{0, false, ~0u}, {0, true, ~0u}};
+  if constexpr (PS) from[2] = {1, false, ShadeFields::kMask};
   for (uint32_t i0 = blockIdx.x * kShadeBlock; i0 < n; i0 += gridDim.x * kShadeBlock) {  // block-uniform
     const uint32_t i = i0 + threadIdx.x;
     ShadeOut R;
@@ -1561,125 +1760,21 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
     if (i < n) {
       const uint32_t q = !PS || i < nh ? i : end - 1u - (i - nh);  // front, then the back downward
       shade_path<TRI_ONLY, PNEE, OV, CR>(S, O, P, col, t_in[q], id_in[q], in.o[q], in.d[q], in.thr[q], R,
-                                     lds_lights ? (const lds_f4v*)s_light : nullptr);
+                                         lds_lights ? (const lds_f4v*)s_light : nullptr);
     }
-    bool res = false;
-    float pt = 0.0f;
-    int32_t pid = -1;
-    if constexpr (PS) {
-      if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
-    }
-    bool drop = false;
-    if constexpr (PS) {
-      if (res && pid < 0 && P.drop_miss) {
-        const V3 add_c = mulv(ld3(R.th), mk(S.bg[0], S.bg[1], S.bg[2]));  // shade_path's miss branch
-        drop = (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
-      }
-      if (drop) {
-        R.alive = res = false;
-        if constexpr (CR) {
-          const uint32_t f = __float_as_uint(R.th.w);
-          reinterpret_cast<uint32_t*>(col + __float_as_uint(R.rd.w))[3] =
-              (((f >> kDepthShift) & kDepthMask) + 1u) | ((f >> kShadowShift) << 16);
-        }
-      }
-    }
-    // The shadow ray: one that provably ends unoccluded (presolve_shadow,
-    // wpt_presolve.h) adds its contribution in this launch, the
-    // read-modify-write k_shadow would do (below, where the other lanes store
-    // their shadow rays), and takes no slot of the shadow stream. The path's
-    // additions keep their order: shade_path adds nothing to col for a path
-    // that emits a shadow ray, and this launch runs after the traversal of
-    // the previous bounce's shadow rays. (After a CR path's count word.)
-    // (Not in the PNEE variant that reads the octree from global memory: with
-    // it that variant needs 24 B of scratch where it had 20.)
-    bool sres = false;
-    if constexpr (PS && !(PNEE && OCT == 0)) {
-      if (R.shadow && P.presolve_shadow)
-        sres = presolve_shadow(S, *S.pre, ld3(R.so), ld3(R.sd), R.so.w, (int32_t)__float_as_uint(R.sd.w));
-    }
-    const uint64_t am = __ballot(R.alive && !res), sm = __ballot(R.shadow && !sres), rm = PS ? __ballot(res) : 0ull;
-    const uint64_t dm = PS ? __ballot(drop) : 0ull, zm = PS ? __ballot(sres) : 0ull;
-    if (lane == 0) {
-      s_off[0][wid] = (uint32_t)__popcll(am);
-      s_off[1][wid] = (uint32_t)__popcll(sm);
-      if constexpr (PS)
-        s_off[2][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 10) | ((uint32_t)__popcll(zm) << 20);
-    }
+    Verdict V{R.alive, false, false, false, 0.0f, -1};
+    if constexpr (PS) V = presolve_out<!(PNEE && OCT == 0), CR>(S, P, col, R);
+    uint32_t cnt[PS ? 3 : 2];
+    const OutMasks M = count_out<PS>(R, V, cnt);
+    if (lane == 0) A.publish(wid, cnt);
     __syncthreads();
-    if constexpr (!PS) {
-      if (wid == 0) {
-        const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
-        uint32_t ia = a, ib = b;
-#pragma unroll
-        for (uint32_t k = 1; k < kWaves; k <<= 1) {
-          const uint32_t ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64);
-          if (lane >= k) { ia += ya; ib += yb; }
-        }
-        unsigned long long base = 0ull;
-        if (lane == kWaves - 1) base = atomicAdd(append, (unsigned long long)ia | ((unsigned long long)ib << 32));
-        const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
-        const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
-        if (lane < kWaves) {
-          s_off[0][lane] = ba + ia - a;
-          s_off[1][lane] = bb + ib - b;
-        }
-      }
-    } else if (wid == 0) {
-      const uint32_t a = lane < kWaves ? s_off[0][lane] : 0u, b = lane < kWaves ? s_off[1][lane] : 0u;
-      const uint32_t c = lane < kWaves ? s_off[2][lane] : 0u;
-      uint32_t ia = a, ib = b, ic = c;
-#pragma unroll
-      for (uint32_t k = 1; k < kWaves; k <<= 1) {
-        const uint32_t ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64), yc = __shfl_up(ic, k, 64);
-        if (lane >= k) { ia += ya; ib += yb; ic += yc; }
-      }
-      const uint32_t tc = (uint32_t)__shfl((int)ic, (int)(kWaves - 1), 64);
-      unsigned long long base = 0ull;
-      // the second counter's distance, made here: as a plain constant the
-      // compiler keeps it in a VGPR across the whole loop (shade_path's peak)
-      // lane kWaves + 1: the shadow rays resolved here, into this bounce's
-      // slot of the block after the presolved counts (kShResWord)
-      uint32_t off;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)(kResWord / 2)));
-      if (lane == kWaves + 1) asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "i"((uint32_t)((kShResWord - 2) / 2)));
-      unsigned long long inc = (unsigned long long)ia | ((unsigned long long)ib << 32);
-      if (lane == kWaves) inc = (unsigned long long)(tc & 0x3ffu) | ((unsigned long long)((tc >> 10) & 0x3ffu) << 32);
-      if (lane == kWaves + 1) inc = (unsigned long long)(tc >> 20);
-      if (lane >= kWaves - 1 && lane <= kWaves + 1) base = atomicAdd(append + (lane == kWaves - 1 ? 0u : off), inc);
-      const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
-      const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
-      const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
-      if (lane < kWaves) {
-        s_off[0][lane] = ba + ia - a;
-        s_off[1][lane] = bb + ib - b;
-        s_off[2][lane] = bc + ((ic - c) & 0x3ffu);
-      }
-    }
+    if (wid == 0)
+      A.reserve(lane, from, [&](const uint32_t(&incl)[PS ? 3 : 2]) {
+        if constexpr (PS) return shade_take<BA>(lane, append, incl[0], incl[1], A.total(incl[2]));
+        else return A.take(append, incl[0], incl[1], lane == kWaves - 1);
+      });
     __syncthreads();
-    if (R.alive) {
-      uint32_t p = s_off[0][wid] + (uint32_t)__popcll(am & below);
-      if constexpr (PS) {
-        if (res) p = end - 1u - (s_off[2][wid] + (uint32_t)__popcll(rm & below));
-      }
-      st_stream(out.o + p, R.ro);
-      st_stream(out.d + p, R.rd);
-      st_stream(out.thr + p, R.th);
-      if constexpr (PS) {
-        if (res) {
-          t_nx[p] = pt;
-          id_nx[p] = pid;
-        }
-      }
-    }
-    if (sres) {
-      add_contribution_xyz(col, R.sc);
-    } else if (R.shadow) {
-      const uint32_t p = s_off[1][wid] + (uint32_t)__popcll(sm & below);
-      st_stream(sh.o + p, R.so);
-      st_stream(sh.d + p, R.sd);
-      st_stream(sh.c + p, R.sc);
-    }
+    store_out<PS, 0>(A, wid, below, M, R, V, out, sh, col, t_nx, id_nx, end);
     __syncthreads();  // s_off is rewritten by the next iteration
   }
 }
@@ -1697,11 +1792,9 @@ __global__ void WPT_SHADE_BOUNDS k_shade(DevScene S, ShadeParams P, RayStream in
 // 0 through count0 as in k_generate_ps; k_extend(0) and k_shade(0) see only
 // those. A primary ray resolved to a miss that adds nothing (P.drop_miss) is
 // only counted, in the high word of res_ctr(0), as k_generate_ps does.
-// What a shaded path emits is handled as k_shade<.., PS = true>(0) handles it,
-// through the counters that launch appends to afterwards for its own paths:
-// the next ray is presolved (front or back of stream 1, its record to t_nx /
-// id_nx, or dropped), the shadow ray goes to the bounce-0 shadow stream or,
-// when presolve_shadow resolves it, is added to col here. One block scan and
+// What a shaded path emits is handled as k_shade<.., PS = true>(0) handles it
+// (presolve_out, store_out), through the counters that launch appends to
+// afterwards for its own paths. One block scan and
 // ONE atomic instruction per kShadeBlock paths (lanes kWaves-1 .. kWaves+4, six
 // addresses; a lane whose increment is 0 stays out): count0, append_ctr(0),
 // the next bounce's presolved slot, the bounce's slot at kShResWord, the
@@ -1729,30 +1822,17 @@ __global__ void __launch_bounds__(kShadeBlock) k_generate_shade(GenParams G, con
                                                                 int32_t* __restrict__ id_nx,
                                                                 uint32_t* __restrict__ counts) {
   constexpr uint32_t kWaves = kShadeBlock / 64;
-  static_assert(kWaves + 4 < 64, "the scan's totals and the other atomic lanes sit in one wave");
-  static_assert(kShadeBlock < 1024, "10-bit fields in the scan's packed columns");
-  // columns: unresolved primaries | survivors (front) | streamed shadow rays |
-  // next rays resolved, dropped << 10, shadow rays resolved << 20 |
-  // primaries dropped, shaded << 10
+  // columns: unresolved primaries | count_out's three | primaries dropped, shaded
+  using BA = BlockAppend<5, kWaves>;
   __shared__ uint32_t s_off[5][kWaves];
   __shared__ f4v s_light[5 * kShadeLights];
-  const bool lds_lights = S.num_lights <= kShadeLights;
-  if (lds_lights) {
-    for (uint32_t k = threadIdx.x; k < 5 * S.num_lights; k += kShadeBlock) {
-      const float4 v = S.lights[k];
-      s_light[k] = f4v{v.x, v.y, v.z, v.w};
-    }
-  }
+  const BA A{s_off};
+  const bool lds_lights = stage_lights(S, s_light);
   __syncthreads();  // the light records
-  OctG O;
-  O.child = S.oct_child;
-  O.cum = S.oct_cum;
+  const OctG O = oct_view<0>(S, nullptr);
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t below = (1ull << lane) - 1ull;
-  const V3 bg = mk(S.bg[0], S.bg[1], S.bg[2]);
-  const V3 add_c = mulv(mk(1.0f, 1.0f, 1.0f), bg);  // shade_path's miss branch
-  const bool adds_nothing =
-      P.drop_miss != 0 && (__float_as_uint(add_c.x) | __float_as_uint(add_c.y) | __float_as_uint(add_c.z)) == 0u;
+  const bool drop_misses = P.drop_miss != 0 && adds_nothing(mk(1.0f, 1.0f, 1.0f), S);
   for (uint32_t i0 = blockIdx.x * kShadeBlock; i0 < n; i0 += gridDim.x * kShadeBlock) {  // block-uniform
     const uint32_t i = i0 + threadIdx.x;
     ShadeOut R;
@@ -1760,7 +1840,7 @@ __global__ void __launch_bounds__(kShadeBlock) k_generate_shade(GenParams G, con
     bool front0 = false, drop0 = false, shaded = false;
     if (i < n) {
       const GenPath g = gen_path(G, part_pix, k0 + i, rnd_off, rnd_base, rnd_list);
-      pix_out[i] = rnd_off ? g.pl : g.pixel;
+      pix_out[i] = path_slot(g, rnd_off, 0u);
       col[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       float t = 0.0f;
       int32_t id = -1;
@@ -1774,7 +1854,7 @@ __global__ void __launch_bounds__(kShadeBlock) k_generate_shade(GenParams G, con
         R.ro = o4;
         R.rd = d4;
         R.th = th4;
-      } else if (id < 0 && adds_nothing) {
+      } else if (id < 0 && drop_misses) {
         drop0 = true;
       } else {
         shaded = true;
@@ -1783,103 +1863,38 @@ __global__ void __launch_bounds__(kShadeBlock) k_generate_shade(GenParams G, con
       }
     }
     // from here on as k_shade<.., PS = true> after its shade_path
-    bool res = false;
-    float pt = 0.0f;
-    int32_t pid = -1;
-    if (R.alive) res = presolve_ray(S, *S.pre, ld3(R.ro), ld3(R.rd), pt, pid);
-    bool drop = false;
-    if (res && pid < 0 && P.drop_miss) {
-      const V3 ac = mulv(ld3(R.th), bg);  // shade_path's miss branch
-      drop = (__float_as_uint(ac.x) | __float_as_uint(ac.y) | __float_as_uint(ac.z)) == 0u;
-    }
-    if (drop) R.alive = res = false;
-    bool sres = false;
-    if (R.shadow && P.presolve_shadow)
-      sres = presolve_shadow(S, *S.pre, ld3(R.so), ld3(R.sd), R.so.w, (int32_t)__float_as_uint(R.sd.w));
-    const uint64_t fm = __ballot(front0), am = __ballot(R.alive && !res), sm = __ballot(R.shadow && !sres);
-    const uint64_t rm = __ballot(res), dm = __ballot(drop), zm = __ballot(sres);
-    const uint64_t d0m = __ballot(drop0), g0m = __ballot(shaded);
-    if (lane == 0) {
-      s_off[0][wid] = (uint32_t)__popcll(fm);
-      s_off[1][wid] = (uint32_t)__popcll(am);
-      s_off[2][wid] = (uint32_t)__popcll(sm);
-      s_off[3][wid] = (uint32_t)__popcll(rm) | ((uint32_t)__popcll(dm) << 10) | ((uint32_t)__popcll(zm) << 20);
-      s_off[4][wid] = (uint32_t)__popcll(d0m) | ((uint32_t)__popcll(g0m) << 10);
-    }
+    const Verdict V = presolve_out<true, false>(S, P, col, R);
+    const uint64_t fm = __ballot(front0);
+    uint32_t cnt[5];
+    cnt[0] = (uint32_t)__popcll(fm);
+    const OutMasks M = count_out<true>(R, V, cnt + 1);
+    cnt[4] = ShadeFields::pack((uint32_t)__popcll(__ballot(drop0)), (uint32_t)__popcll(__ballot(shaded)));
+    if (lane == 0) A.publish(wid, cnt);
     __syncthreads();
-    if (wid == 0) {
-      const bool in = lane < kWaves;
-      const uint32_t f = in ? s_off[0][lane] : 0u, a = in ? s_off[1][lane] : 0u, b = in ? s_off[2][lane] : 0u;
-      const uint32_t c = in ? s_off[3][lane] : 0u, e = in ? s_off[4][lane] : 0u;
-      uint32_t jf = f, ia = a, ib = b, ic = c, ie = e;
-#pragma unroll
-      for (uint32_t k = 1; k < kWaves; k <<= 1) {
-        const uint32_t yf = __shfl_up(jf, k, 64), ya = __shfl_up(ia, k, 64), yb = __shfl_up(ib, k, 64);
-        const uint32_t yc = __shfl_up(ic, k, 64), ye = __shfl_up(ie, k, 64);
-        if (lane >= k) { jf += yf; ia += ya; ib += yb; ic += yc; ie += ye; }
-      }
-      // lane kWaves - 1 holds every total
-      const uint32_t tf = (uint32_t)__shfl((int)jf, (int)(kWaves - 1), 64);
-      const uint32_t tc = (uint32_t)__shfl((int)ic, (int)(kWaves - 1), 64);
-      const uint32_t te = (uint32_t)__shfl((int)ie, (int)(kWaves - 1), 64);
-      // this lane's counter (u32 index in counts) and increment
-      uint32_t word = 2u;  // append_ctr(0): survivors | streamed shadow rays
-      unsigned long long inc = (unsigned long long)ia | ((unsigned long long)ib << 32);
-      if (lane == kWaves) {  // res_ctr(1): next rays resolved | dropped
-        word = (uint32_t)kResWord + 2u;
-        inc = (unsigned long long)(tc & 0x3ffu) | ((unsigned long long)((tc >> 10) & 0x3ffu) << 32);
-      } else if (lane == kWaves + 1) {  // bounce 0's shadow rays resolved here
-        word = (uint32_t)kShResWord;
-        inc = (unsigned long long)(tc >> 20);
-      } else if (lane == kWaves + 2) {  // count0 (the word after it is unused)
-        word = 0u;
-        inc = (unsigned long long)tf;
-      } else if (lane == kWaves + 3) {  // res_ctr(0)'s high word: primaries dropped
-        word = (uint32_t)kResWord;
-        inc = (unsigned long long)(te & 0x3ffu) << 32;
-      } else if (lane == kWaves + 4) {  // primaries shaded here
-        word = (uint32_t)kGenShadeWord;
-        inc = (unsigned long long)(te >> 10);
-      }
-      unsigned long long base = 0ull;
-      if (lane >= kWaves - 1 && lane <= kWaves + 4 && inc != 0ull)
-        base = atomicAdd(reinterpret_cast<unsigned long long*>(counts + word), inc);
-      const uint32_t ba = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves - 1), 64);
-      const uint32_t bb = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)(kWaves - 1), 64);
-      const uint32_t bc = (uint32_t)__shfl((int)(uint32_t)base, (int)kWaves, 64);
-      const uint32_t bf = (uint32_t)__shfl((int)(uint32_t)base, (int)(kWaves + 2), 64);
-      if (in) {
-        s_off[0][lane] = bf + jf - f;
-        s_off[1][lane] = ba + ia - a;
-        s_off[2][lane] = bb + ib - b;
-        s_off[3][lane] = bc + ((ic - c) & 0x3ffu);
-      }
-    }
+    if (wid == 0)
+      A.reserve(lane,
+                {{3, false, ~0u}, {0, false, ~0u}, {0, true, ~0u}, {1, false, ShadeFields::kMask}, {-1, false, 0u}},
+                [&](const uint32_t(&incl)[5]) {
+                  const uint32_t tf = A.total(incl[0]), te = A.total(incl[4]);
+                  // first append_ctr(0), res_ctr(1), bounce 0's slot at kShResWord (counts + 2: append_ctr(0))
+                  auto t = shade_take<BA>(lane, reinterpret_cast<u64*>(counts + 2), incl[1], incl[2], A.total(incl[3]));
+                  if (lane == kWaves + 2)  // count0 (the word after it is unused)
+                    t = A.take(counts, tf, 0u, true);
+                  else if (lane == kWaves + 3)  // res_ctr(0)'s high word: primaries dropped
+                    t = A.take(counts + kResWord, 0u, ShadeFields::get(te, 0), true);
+                  else if (lane == kWaves + 4)  // primaries shaded here
+                    t = A.take(counts + kGenShadeWord, ShadeFields::top(te, 1), 0u, true);
+                  t.go = t.go && t.inc != 0ull;  // a lane whose increment is 0 stays out
+                  return t;
+                });
     __syncthreads();
     if (front0) {
-      const uint32_t p = s_off[0][wid] + (uint32_t)__popcll(fm & below);
+      const uint32_t p = A.at(0, wid, (uint32_t)__popcll(fm & below));
       s0.thr[p] = R.th;
       s0.o[p] = R.ro;
       s0.d[p] = R.rd;
-    } else if (R.alive) {
-      uint32_t p = s_off[1][wid] + (uint32_t)__popcll(am & below);
-      if (res) p = n - 1u - (s_off[3][wid] + (uint32_t)__popcll(rm & below));
-      st_stream(out.o + p, R.ro);
-      st_stream(out.d + p, R.rd);
-      st_stream(out.thr + p, R.th);
-      if (res) {
-        t_nx[p] = pt;
-        id_nx[p] = pid;
-      }
-    }
-    if (sres) {
-      add_contribution_xyz(col, R.sc);
-    } else if (R.shadow) {
-      const uint32_t p = s_off[2][wid] + (uint32_t)__popcll(sm & below);
-      st_stream(sh.o + p, R.so);
-      st_stream(sh.d + p, R.sd);
-      st_stream(sh.c + p, R.sc);
-    }
+    } else
+      store_out<true, 1>(A, wid, below, M, R, V, out, sh, col, t_nx, id_nx, n);
     __syncthreads();  // s_off is rewritten by the next iteration
   }
 }
@@ -1922,8 +1937,7 @@ struct WaveFeed {
 // ---------------------------------------------------------------------------
 // Test hook (Renderer::photon_sample): photon_sample of n points, point i on
 // the xorshift32 state st_in[i], reading the octree as k_shade<.., PNEE, OCT>
-// does. The staging loop and the views are k_shade's, restated here so that
-// k_shade's own code does not change.
+// does (oct_view).
 // ---------------------------------------------------------------------------
 template <int OCT>
 __global__ void __launch_bounds__(kShadeBlock) k_photon_sample(DevScene S, uint32_t n, const float* __restrict__ pts,
@@ -1931,24 +1945,8 @@ __global__ void __launch_bounds__(kShadeBlock) k_photon_sample(DevScene S, uint3
                                                                uint32_t* __restrict__ light, float* __restrict__ pdf,
                                                                uint32_t* __restrict__ st_out) {
   extern __shared__ uint32_t s_oct[];
-  if (OCT != 0) {
-    const uint32_t nc = S.oct_nodes, nw = S.oct_lds_words;
-    for (uint32_t k = threadIdx.x; k < nw; k += kShadeBlock)
-      s_oct[k] = k < nc ? S.oct_child[k] : __float_as_uint(S.oct_cum[k - nc]);
-  }
+  const OctView<OCT> O = oct_view<OCT>(S, s_oct);
   __syncthreads();
-  using OV = std::conditional_t<OCT == 2, OctL2, std::conditional_t<OCT == 1, OctL1, OctG>>;
-  OV O;
-  if constexpr (OCT == 2) {
-    O.child = (const lds_u32*)s_oct;
-    O.cum = (const lds_f32*)(s_oct + S.oct_nodes);
-  } else if constexpr (OCT == 1) {
-    O.child = (const lds_u32*)s_oct;
-    O.cum = S.oct_cum;
-  } else {
-    O.child = S.oct_child;
-    O.cum = S.oct_cum;
-  }
   for (uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x; i < n; i += gridDim.x * kShadeBlock) {
     uint32_t s = st_in[i], li = 0;
     float p = 0.0f;
@@ -3349,6 +3347,13 @@ void Renderer::batch_counts(const Batch& B, const uint32_t* hc) {
   stats_.bounces += (uint64_t)B.b;
 }
 
+// What the shade kernels of a batch get. Without a light guard the light lies
+// inside an ordinary guard, whose box the ray's target is in: next to nothing
+// resolves (the museum), so they do not try the shadow presolve.
+auto Renderer::shade_params() const {
+  return ShadeParams{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
+}
+
 // Lanes, slices and bounce 0 of batch B (k_generate on each lane's stream,
 // after the main stream's work so far: reset, round planning, k_spec_plan).
 bool Renderer::batch_begin(Batch& B, std::string& err) {
@@ -3378,9 +3383,9 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   B.pnee = left_type_ == 2 || right_type_ == 2;
   // k_generate_shade shades the primary rays it resolves (WPT_OPT_GEN_SHADE);
   // PNEE batches (k_shade stages the octree) and stock batches (the count
-  // word) keep k_generate_ps. SP: batch_advance's.
+  // word) keep k_generate_ps.
   const bool gen_shade = gen_shade_ && B.presolve && !B.pnee && !B.stock;
-  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
+  const ShadeParams SP = shade_params();
   if (profiling_ && !B.async) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
   for (int i = 0; i < B.nl; i++) {
@@ -3450,10 +3455,7 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
 // of an RR-only batch must come back first. block: wait for such counts;
 // else return with B in kCountWait when they have not landed yet.
 bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
-  // Without a light guard the light lies inside an ordinary guard, whose box
-  // the ray's target is in: next to nothing resolves (the museum), so k_shade
-  // does not try.
-  const ShadeParams SP{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
+  const ShadeParams SP = shade_params();
   // the paths of C's lane in stream rin, to their end, one lane each
   auto launch_finish = [&](const LaunchCtx& C, const RayStream& rin, uint32_t g, bool pn) -> bool {
     const PathSet& L = *C.ps;
@@ -5250,28 +5252,24 @@ bool Renderer::shadow_rays(size_t n, const float* pq, const int32_t* light, uint
   std::vector<float4> o(n), d(n);
   for (size_t i = 0; i < n; i++) {
     const float* r = pq + 6 * i;
-    const V3 p = mk(r[0], r[1], r[2]), q = mk(r[3], r[4], r[5]);
-    V3 dir = sub(q, p);
-    const float dl = len(dir);
-    dir = divs(dir, dl);
-    const V3 org = add(p, scale(dir, kEpsilon));
+    V3 org, dir;
+    float dl;
+    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), org, dir, dl);
     o[i] = make_float4(org.x, org.y, org.z, dl);
     d[i] = make_float4(dir.x, dir.y, dir.z, u2f((uint32_t)light[i]));
   }
   uint8_t* dq = nullptr;
   HIP_OK(hipMalloc(&dq, n));
+  const std::unique_ptr<uint8_t, void (*)(uint8_t*)> free_dq(dq, [](uint8_t* p) { (void)hipFree(p); });  // any return
   const uint32_t nn = (uint32_t)n;
   const PathSet& L = lanes_[0];
   HIP_OK(hipMemcpyAsync(L.so, o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(L.sd, d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(L.counts, &nn, 4, hipMemcpyHostToDevice, stream_));
-  const bool ok = launch_shadow(lane0_ctx(counting_), L.counts, dq, err);
-  if (ok) {
-    HIP_OK(hipMemcpyAsync(occ, dq, n, hipMemcpyDeviceToHost, stream_));
-    HIP_OK(hipStreamSynchronize(stream_));
-  }
-  (void)hipFree(dq);
-  return ok;
+  if (!launch_shadow(lane0_ctx(counting_), L.counts, dq, err)) return false;
+  HIP_OK(hipMemcpyAsync(occ, dq, n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return true;
 }
 
 }  // namespace wpt
