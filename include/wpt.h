@@ -273,6 +273,30 @@ float wpt_seq_sum_chunks(const float* v, uint64_t n);
  * (k_sum_chunks / k_sum_scan / k_sum_eff, as every adaptive round does), the
  * walk on the host: *out = the sum. For its tests; needs wpt_init. */
 int wpt_seq_sum_device(const float* v, uint64_t n, float* out);
+/* Test hook: the error estimate of an adaptive round (sampling_strategy.rs:
+ * 122-144) as the session's rounds run it (the same kernels, launch geometry
+ * and host walk), on the caller's frame of W x H pixels: acc3 = W*H*3 f32
+ * sums, cnt = W*H sample counts. half: 0 the left screen half (x < W/2), 1
+ * the right one. mse_out = that half's errors in the half's raster order (its
+ * width x H floats; none for an empty half), stats3_out = {sum, min, max} as
+ * the planning kernel receives them. Works in buffers of its own: the
+ * session's frame, rounds and stock stay as they are. Needs wpt_init;
+ * WPT_ERR_INVALID_ARG for a null pointer, half > 1, W*H == 0 or W*H >= 2^32. */
+int wpt_adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, uint32_t half, float* mse_out,
+                       float* stats3_out);
+/* Test hook: the planning part of a round of screen half `half` (:146-172;
+ * first != 0: the round after a reset, 4 samples per pixel; adaptive == 0: a
+ * random half's round, 1 sample per pixel) from the caller's errors mse_in
+ * (the half's raster order), stats3_in = {sum, min, max} and counts cnt_in
+ * (W*H): count_out = samples per pixel of the frame (W*H; the other half's
+ * are 0), offset_out = their exclusive prefix (W*H + 1; the last entry is the
+ * round's length), base_out = the pixels' counts before the round (W*H), samp
+ * = the RGBA sampling view (W*H*4), in and out: an estimating round repaints
+ * the half, everything else stays as passed in. Same session rules and errors
+ * as wpt_adaptive_error. */
+int wpt_adaptive_plan(uint32_t W, uint32_t H, uint32_t half, int32_t first, int32_t adaptive, const float* mse_in,
+                      const float* stats3_in, const uint32_t* cnt_in, uint32_t* count_out, uint32_t* offset_out,
+                      uint32_t* base_out, uint8_t* samp);
 
 /* stats: out[0..39] = paths, rays (primary+extension), shadow rays, BVH node
  * visits, primitive tests, bounce iterations, then per kernel (extend, shadow):

@@ -51,6 +51,8 @@ def lib():
         L.oracle_adaptive_compute.argtypes = [c_p, ctypes.c_uint64, c_int]
         L.oracle_adaptive_read.argtypes = [c_p, c_p, c_p, c_p]
         L.oracle_adaptive_free.argtypes = [c_p]
+        L.oracle_adaptive_error.argtypes = [c_u32, c_u32, c_p, c_p, c_int, c_p, c_p]
+        L.oracle_adaptive_plan.argtypes = [c_u32, c_u32, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
         L.oracle_photon_tree.restype = c_sz
         L.oracle_photon_tree.argtypes = [c_p, c_u32, c_int, c_p, c_p, c_p]
         L.oracle_set_photons.argtypes = [c_p, c_sz, c_p, c_p, c_p]
@@ -228,6 +230,44 @@ class AdaptiveSession:
                 _L.oracle_adaptive_free(self.h)
         except Exception:  # noqa: BLE001
             pass
+
+
+def half_width(width, half):
+    """Columns of screen half `half` (0 left, 1 right) of a viewport."""
+    return width - width // 2 if half else width // 2
+
+
+def adaptive_error(acc, cnt, half):
+    """Stage 1 of an adaptive round (sampling_strategy.rs:122-144) on a frame
+    acc (H, W, 3) f32 sums / cnt (H, W) u32 counts: the errors of screen half
+    `half` (H, its width) and stats = f32 {sum, min, max}."""
+    a = np.ascontiguousarray(acc, dtype=np.float32)
+    c = np.ascontiguousarray(cnt, dtype=np.uint32)
+    H, W = c.shape
+    assert a.shape == (H, W, 3)
+    mse = np.empty((H, half_width(W, half)), dtype=np.float32)
+    stats = np.empty(3, dtype=np.float32)
+    lib().oracle_adaptive_error(W, H, a.ctypes.data, c.ctypes.data, int(half), mse.ctypes.data, stats.ctypes.data)
+    return mse, stats
+
+
+def adaptive_plan(width, height, half, mse, stats, cnt, samp, first=False, adaptive=True):
+    """Stage 2 (:146-172): from the half's errors and stats, (count (H, W),
+    offset (W*H + 1), base (H, W), the view (H, W, 4) u8 with the half
+    repainted; samp is not modified)."""
+    m = np.ascontiguousarray(mse, dtype=np.float32)
+    s = np.ascontiguousarray(stats, dtype=np.float32)
+    c = np.ascontiguousarray(cnt, dtype=np.uint32)
+    view = np.array(samp, dtype=np.uint8, order="C", copy=True)
+    assert m.size == height * half_width(width, half) and s.shape == (3,)
+    assert c.size == width * height and view.size == 4 * width * height
+    count = np.empty((height, width), dtype=np.uint32)
+    offset = np.empty(width * height + 1, dtype=np.uint32)
+    base = np.empty((height, width), dtype=np.uint32)
+    lib().oracle_adaptive_plan(width, height, int(half), int(bool(first)), int(bool(adaptive)), m.ctypes.data,
+                               s.ctypes.data, c.ctypes.data, count.ctypes.data, offset.ctypes.data, base.ctypes.data,
+                               view.ctypes.data)
+    return count, offset, base, view.reshape(height, width, 4)
 
 
 def torus_trace(loc, big_r, small_r, rays):

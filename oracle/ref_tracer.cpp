@@ -604,22 +604,14 @@ void oracle_photon_leaf(void* p, uint32_t seed, int threads, size_t n, const flo
 // round's paths are the half's pixels in raster order, each pixel's samples
 // consecutive, sample s of pixel p on stream path_seed(seed, p, s).
 // ---------------------------------------------------------------------------
-struct AdaptiveSession {
-  OracleHandle* h;
+// The two stages of AdaptiveSamplingStrategy::next() (:122-176) as functions of
+// their inputs alone, so that a test can run either on a frame of its own
+// (oracle_adaptive_error / oracle_adaptive_plan below); AdaptiveSession's
+// plan_round is the two chained.
+struct FrameView {
   uint32_t W, H;
-  Camera cam;
-  int type[2], adaptive[2], max_depth;
-  uint32_t seed;
-  std::vector<float> acc;       // W*H*3 (RenderTarget::acc_buffer)
-  std::vector<uint32_t> cnt;    // acc_count
-  std::vector<uint8_t> samp;    // SimpleRenderTarget (sampling view)
-  struct Rounds {
-    std::vector<uint32_t> off, base;   // per pixel: prefix offsets of the round's samples, samples before it
-    uint64_t total = 0, pos = 0;
-    uint32_t idx = 0;
-  } rounds[2];
-  PathStats st;
-
+  const float* acc;     // W*H*3 sums
+  const uint32_t* cnt;  // W*H counts
   // render_target.rs:75-79 / 214-216
   Vec3 read_clamped(uint32_t x, uint32_t y) const {
     size_t i = (size_t)W * y + x;
@@ -650,52 +642,120 @@ struct AdaptiveSession {
       }
     return v3(a.x / sum, a.y / sum, a.z / sum);
   }
-  static Vec3 mix_color(float v) {  // sampling_strategy.rs:222-230
-    if (v < 0.5f) return v3(0, 1, 0) * (1.0f - 2.0f * v) + v3(0, 0, 1) * 2.0f * v;
-    return v3(0, 0, 1) * (1.0f - 2.0f * (v - 0.5f)) + v3(1, 0, 0) * 2.0f * (v - 0.5f);
+};
+
+// Stage 1 (:122-144): the errors of screen half hh in the half's raster order
+// and stats = {mse_sum, mse_min, mse_max} (the sequential f32 sum; the folds
+// start at +inf / -inf, which an empty half keeps).
+static void adaptive_error(const FrameView& F, int hh, std::vector<float>& mse, float stats[3]) {
+  uint32_t half = F.W / 2;
+  uint32_t x0 = hh ? half : 0, rw = hh ? F.W - half : half;
+  mse.assign((size_t)rw * F.H, 0.0f);
+  float mse_sum = 0.0f, mse_min = INFINITY, mse_max = -INFINITY;
+  for (uint32_t y = 0; y < F.H; y++)
+    for (uint32_t x = 0; x < rw; x++) {
+      Vec3 v0 = F.read_clamped(x0 + x, y);
+      Vec3 v1 = F.gauss((int)(x0 + x), (int)y, 1);
+      Vec3 v2 = F.gauss((int)(x0 + x), (int)y, 2);
+      float m = fmaxf(len_sq(v0 - v1), len_sq(v0 - v2));
+      mse[(size_t)y * rw + x] = m;
+      mse_sum += m;
+      mse_min = fminf(mse_min, m);
+      mse_max = fmaxf(mse_max, m);
+    }
+  stats[0] = mse_sum;
+  stats[1] = mse_min;
+  stats[2] = mse_max;
+}
+
+static Vec3 mix_color(float v) {  // sampling_strategy.rs:222-230
+  if (v < 0.5f) return v3(0, 1, 0) * (1.0f - 2.0f * v) + v3(0, 0, 1) * 2.0f * v;
+  return v3(0, 0, 1) * (1.0f - 2.0f * (v - 0.5f)) + v3(1, 0, 0) * 2.0f * (v - 0.5f);
+}
+
+// Stage 2 (:146-172 and the round schedule's other two cases): the samples
+// each pixel of the frame gets in half hh's next round (c, W*H; the other
+// half's pixels 0) and, for an estimating round, the half's sampling view.
+static void adaptive_plan(uint32_t W, uint32_t H, int hh, bool first, bool adaptive, const float* mse,
+                          const float stats[3], std::vector<uint32_t>& c, uint8_t* samp) {
+  size_t np = (size_t)W * H;
+  c.assign(np, 0);
+  uint32_t half = W / 2;
+  uint32_t x0 = hh ? half : 0, rw = hh ? W - half : half;
+  if (!adaptive) {  // RandomSamplingStrategy stand-in: one sample per pixel of the half
+    for (uint32_t y = 0; y < H; y++)
+      for (uint32_t x = x0; x < x0 + rw; x++) c[(size_t)y * W + x] = 1;
+  } else if (first) {  // reset (:198-219): 4 samples per pixel
+    for (uint32_t y = 0; y < H; y++)
+      for (uint32_t x = x0; x < x0 + rw; x++) c[(size_t)y * W + x] = 4;
+  } else {
+    const float mse_sum = stats[0], mse_min = stats[1], mse_max = stats[2];
+    float mse_avg = mse_sum / (float)(rw * H);
+    for (uint32_t y = 0; y < H; y++)
+      for (uint32_t x = 0; x < rw; x++) {
+        float m = mse[(size_t)y * rw + x];
+        float scaled = m < mse_avg ? 0.5f * ((m - mse_min) / (mse_avg - mse_min))
+                                   : 0.5f + 0.5f * ((m - mse_avg) / (mse_max - mse_avg));
+        scaled = fmaxf(fminf(scaled, 1.0f), 0.0f);
+        size_t pix = (size_t)y * W + x0 + x;
+        c[pix] = (uint32_t)ceilf(1.0f + scaled * 32.0f);
+        Vec3 vis = mse_min == mse_max ? v3(0, 0, 0) : mix_color(scaled);
+        samp[4 * pix] = (uint8_t)(fmaxf(fminf(vis.x, 1.0f), 0.0f) * 255.0f);
+        samp[4 * pix + 1] = (uint8_t)(fmaxf(fminf(vis.y, 1.0f), 0.0f) * 255.0f);
+        samp[4 * pix + 2] = (uint8_t)(fmaxf(fminf(vis.z, 1.0f), 0.0f) * 255.0f);
+      }
   }
+}
+
+// The stages on a caller's frame. oracle_adaptive_error: mse = the half's
+// errors (its width x H), stats3 = {sum, min, max}. oracle_adaptive_plan:
+// count (W*H), offset (W*H + 1, the exclusive prefix and the round total),
+// base (W*H, = cnt) and the RGBA view samp (W*H*4, updated in place).
+void oracle_adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, int half, float* mse,
+                           float* stats3) {
+  std::vector<float> m;
+  adaptive_error(FrameView{W, H, acc3, cnt}, half, m, stats3);
+  if (!m.empty()) memcpy(mse, m.data(), sizeof(float) * m.size());
+}
+void oracle_adaptive_plan(uint32_t W, uint32_t H, int half, int first, int adaptive, const float* mse,
+                          const float* stats3, const uint32_t* cnt, uint32_t* count, uint32_t* offset, uint32_t* base,
+                          uint8_t* samp) {
+  std::vector<uint32_t> c;
+  adaptive_plan(W, H, half, first != 0, adaptive != 0, mse, stats3, c, samp);
+  size_t np = (size_t)W * H;
+  offset[0] = 0;
+  for (size_t p = 0; p < np; p++) {
+    count[p] = c[p];
+    offset[p + 1] = offset[p] + c[p];
+    base[p] = cnt[p];
+  }
+}
+
+struct AdaptiveSession {
+  OracleHandle* h;
+  uint32_t W, H;
+  Camera cam;
+  int type[2], adaptive[2], max_depth;
+  uint32_t seed;
+  std::vector<float> acc;       // W*H*3 (RenderTarget::acc_buffer)
+  std::vector<uint32_t> cnt;    // acc_count
+  std::vector<uint8_t> samp;    // SimpleRenderTarget (sampling view)
+  struct Rounds {
+    std::vector<uint32_t> off, base;   // per pixel: prefix offsets of the round's samples, samples before it
+    uint64_t total = 0, pos = 0;
+    uint32_t idx = 0;
+  } rounds[2];
+  PathStats st;
+
   void plan_round(int hh) {
     size_t np = (size_t)W * H;
-    std::vector<uint32_t> c(np, 0);
-    uint32_t half = W / 2;
-    uint32_t x0 = hh ? half : 0, rw = hh ? W - half : half;
+    std::vector<uint32_t> c;
     Rounds& R = rounds[hh];
-    if (!adaptive[hh]) {  // RandomSamplingStrategy stand-in: one sample per pixel of the half
-      for (uint32_t y = 0; y < H; y++)
-        for (uint32_t x = x0; x < x0 + rw; x++) c[(size_t)y * W + x] = 1;
-    } else if (R.idx == 0) {  // reset (:198-219): 4 samples per pixel
-      for (uint32_t y = 0; y < H; y++)
-        for (uint32_t x = x0; x < x0 + rw; x++) c[(size_t)y * W + x] = 4;
-    } else {
-      // next() (:122-176)
-      std::vector<float> mse((size_t)rw * H);
-      float mse_sum = 0.0f, mse_min = INFINITY, mse_max = -INFINITY;
-      for (uint32_t y = 0; y < H; y++)
-        for (uint32_t x = 0; x < rw; x++) {
-          Vec3 v0 = read_clamped(x0 + x, y);
-          Vec3 v1 = gauss((int)(x0 + x), (int)y, 1);
-          Vec3 v2 = gauss((int)(x0 + x), (int)y, 2);
-          float m = fmaxf(len_sq(v0 - v1), len_sq(v0 - v2));
-          mse[(size_t)y * rw + x] = m;
-          mse_sum += m;
-          mse_min = fminf(mse_min, m);
-          mse_max = fmaxf(mse_max, m);
-        }
-      float mse_avg = mse_sum / (float)(rw * H);
-      for (uint32_t y = 0; y < H; y++)
-        for (uint32_t x = 0; x < rw; x++) {
-          float m = mse[(size_t)y * rw + x];
-          float scaled = m < mse_avg ? 0.5f * ((m - mse_min) / (mse_avg - mse_min))
-                                     : 0.5f + 0.5f * ((m - mse_avg) / (mse_max - mse_avg));
-          scaled = fmaxf(fminf(scaled, 1.0f), 0.0f);
-          size_t pix = (size_t)y * W + x0 + x;
-          c[pix] = (uint32_t)ceilf(1.0f + scaled * 32.0f);
-          Vec3 vis = mse_min == mse_max ? v3(0, 0, 0) : mix_color(scaled);
-          samp[4 * pix] = (uint8_t)(fmaxf(fminf(vis.x, 1.0f), 0.0f) * 255.0f);
-          samp[4 * pix + 1] = (uint8_t)(fmaxf(fminf(vis.y, 1.0f), 0.0f) * 255.0f);
-          samp[4 * pix + 2] = (uint8_t)(fmaxf(fminf(vis.z, 1.0f), 0.0f) * 255.0f);
-        }
-    }
+    std::vector<float> mse;
+    float stats[3] = {0.0f, 0.0f, 0.0f};
+    const bool first = R.idx == 0;
+    if (adaptive[hh] && !first) adaptive_error(FrameView{W, H, acc.data(), cnt.data()}, hh, mse, stats);  // next() (:122-144)
+    adaptive_plan(W, H, hh, first, adaptive[hh] != 0, mse.data(), stats, c, samp.data());
     R.off.assign(np + 1, 0);
     R.base.assign(np, 0);
     for (size_t p = 0; p < np; p++) {

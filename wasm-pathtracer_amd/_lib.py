@@ -82,6 +82,8 @@ _SIGS = {
     "wpt_seq_sum": (ctypes.c_float, [c_p, ctypes.c_uint64]),
     "wpt_seq_sum_chunks": (ctypes.c_float, [c_p, ctypes.c_uint64]),
     "wpt_seq_sum_device": (ctypes.c_int, [c_p, ctypes.c_uint64, c_p]),
+    "wpt_adaptive_error": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_u32, c_p, c_p]),
+    "wpt_adaptive_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_lights": (ctypes.c_int, [c_p, c_p]),
     "wpt_debug_scene_free": (None, [c_p]),
     "wpt_debug_scene_new_gpu": (c_p, [c_i32, c_p, c_sz]),

@@ -581,6 +581,33 @@ int wpt_seq_sum_device(const float* v, uint64_t n, float* out) {
   return WPT_OK;
 }
 
+int wpt_adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, uint32_t half, float* mse_out,
+                       float* stats3_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (!acc3 || !cnt || !mse_out || !stats3_out) return fail(WPT_ERR_INVALID_ARG, "null pointer");
+  if (half > 1) return fail(WPT_ERR_INVALID_ARG, "adaptive_error: half 0 or 1");
+  if ((uint64_t)W * H == 0 || (uint64_t)W * H >= (1ull << 32)) return fail(WPT_ERR_INVALID_ARG, "bad frame size");
+  std::string err;
+  if (!g_session->renderer.adaptive_error(W, H, acc3, cnt, (int)half, mse_out, stats3_out, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_adaptive_plan(uint32_t W, uint32_t H, uint32_t half, int32_t first, int32_t adaptive, const float* mse_in,
+                      const float* stats3_in, const uint32_t* cnt_in, uint32_t* count_out, uint32_t* offset_out,
+                      uint32_t* base_out, uint8_t* samp) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (!mse_in || !stats3_in || !cnt_in || !count_out || !offset_out || !base_out || !samp)
+    return fail(WPT_ERR_INVALID_ARG, "null pointer");
+  if (half > 1) return fail(WPT_ERR_INVALID_ARG, "adaptive_plan: half 0 or 1");
+  if ((uint64_t)W * H == 0 || (uint64_t)W * H >= (1ull << 32)) return fail(WPT_ERR_INVALID_ARG, "bad frame size");
+  std::string err;
+  if (!g_session->renderer.adaptive_plan(W, H, (int)half, first != 0, adaptive != 0, mse_in, stats3_in, cnt_in,
+                                         count_out, offset_out, base_out, samp, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 int wpt_comm_destroy(void) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   g_session->drop_comm();

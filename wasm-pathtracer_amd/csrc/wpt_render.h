@@ -351,6 +351,14 @@ class Renderer {
   // the adaptive rounds' sum path on host data (tests): chunk effects on the
   // device, the walk on the host
   bool seq_sum_device(const float* v, uint64_t n, float& out, std::string& err);
+  // Test hooks: the two parts of plan_round (estimate_errors, plan_counts) on
+  // a host frame of W x H pixels, in scratch buffers; the session's frame,
+  // rounds and stock are not touched.
+  bool adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, int half, float* mse_out,
+                      float* stats3, std::string& err);
+  bool adaptive_plan(uint32_t W, uint32_t H, int half, bool first, bool adaptive, const float* mse,
+                     const float* stats3, const uint32_t* cnt, uint32_t* count, uint32_t* offset, uint32_t* base,
+                     uint8_t* samp, std::string& err);
   const Stats& stats() const { return stats_; }
   const KernelTimes& times() const { return times_; }
   void clear_stats() {
@@ -397,6 +405,30 @@ class Renderer {
   bool compute_half(int h, uint64_t n, std::string& err);
   bool merge_random_halves(uint64_t nl, uint64_t nr, bool& merged, std::string& err);
   bool plan_round(int h, std::string& err);
+  // plan_round's buffers and its two parts, which the wpt_adaptive_* hooks
+  // run on frames of their own: element counts of the buffers (one formula
+  // for both), a half's error estimate, the round's counts and offsets
+  struct RoundSizes {
+    size_t scan_sums;  // block sums of the offsets' scan (+ 1)
+    size_t mse;        // a half's errors, then the {min, max} keys
+    size_t bmm;        // per-tile {min, max} keys
+    size_t chunks;     // chunks of the errors' sum (+ 1)
+    size_t fetch;      // packed elements of the chunks the walk re-sums
+  };
+  static RoundSizes round_sizes(uint32_t w, uint32_t h, uint32_t pn);
+  struct ErrorBufs {
+    float *d_mse, *h_mse;
+    uint32_t* d_bmm;
+    double* d_s64;
+    ChunkEff *d_eff, *h_eff;
+    uint32_t *d_need, *d_list, *h_list;
+    float *d_fb, *h_fb;
+  };
+  bool estimate_errors(const float4* acc, const uint32_t* cnt_px, uint32_t W, uint32_t H, int h, const ErrorBufs& B,
+                       float stats[3], std::string& err);
+  bool plan_counts(uint32_t W, uint32_t H, uint32_t pn, int h, bool adaptive, bool first, const float stats[3],
+                   const uint32_t* cnt_px, const float* mse_l, const float* mse_r, uint32_t* rc, uint32_t* rbase,
+                   uint32_t* sums, uint8_t* samp, uint32_t* h_total, std::string& err);
   bool exchange_frame(std::string& err);
   bool plan_slice(int h, uint64_t a, uint64_t b, uint64_t& local, std::string& err);
   void free_rounds();

@@ -4751,6 +4751,99 @@ struct SumFetch {
   }
 };
 
+// Element counts of the round buffers of a w x h viewport whose rounds are
+// planned over pn pixels.
+Renderer::RoundSizes Renderer::round_sizes(uint32_t w, uint32_t h, uint32_t pn) {
+  RoundSizes Z;
+  const size_t np = (size_t)w * h;
+  Z.scan_sums = ((size_t)pn + 1 + kScanChunk - 1) / kScanChunk + 1;
+  // per half: np errors, then the {min, max} keys k_mm_reduce leaves
+  Z.mse = np + 2;
+  // per-tile {min, max} keys of k_mse_tiled (a half's tiles)
+  Z.bmm = 2 * ((size_t)(w / kMseTile + 2) * (h / kMseTile + 1));
+  Z.chunks = (np + kSumChunk - 1) / kSumChunk + 1;
+  Z.fetch = (size_t)kSumFetch * kSumChunk;
+  return Z;
+}
+
+// The error estimate of screen half h of the W x H frame acc / cnt
+// (wpt_adaptive.h): the half's errors into B.d_mse in its raster order,
+// stats = {mse_sum, mse_min, mse_max}.
+bool Renderer::estimate_errors(const float4* acc, const uint32_t* cnt_px, uint32_t W, uint32_t H, int h,
+                               const ErrorBufs& B, float stats[3], std::string& err) {
+  // per-pixel error, min and max on the GPU; mse_sum on the host: the
+  // reference's sequential f32 sum in raster order, in binade segments of
+  // integer increments (wpt_seqsum.h) instead of one dependent add chain
+  const uint32_t half = W / 2, np = W * H;
+  const uint32_t x0 = h ? half : 0u, x1 = h ? W : half;
+  const uint32_t cnt = (x1 - x0) * H;
+  if (!cnt) {  // an empty half: the sum of nothing, the folds' start values
+    stats[0] = 0.0f;
+    stats[1] = INFINITY;
+    stats[2] = -INFINITY;
+    return true;
+  }
+  uint32_t* mm = reinterpret_cast<uint32_t*>(B.d_mse + np);
+  const dim3 tiles((x1 - x0 + kMseTile - 1) / kMseTile, (H + kMseTile - 1) / kMseTile);
+  // the errors' sum: chunk effects on the device, walked on the host; the
+  // chunks the walk will likely re-sum come with them (k_sum_pack), any
+  // other one it re-sums is fetched on demand (SumFetch)
+  const uint32_t nch = (cnt + kSumChunk - 1) / kSumChunk;
+  k_mse_tiled<<<tiles, kBlock, 0, stream_>>>(acc, cnt_px, W, H, x0, x1, B.d_mse, B.d_bmm);
+  k_mm_reduce<<<1, 1024, 0, stream_>>>(B.d_bmm, tiles.x * tiles.y, mm);
+  const uint32_t wb = (uint32_t)(((uint64_t)nch * 64u + kBlock - 1) / kBlock);
+  k_sum_chunks<<<wb, kBlock, 0, stream_>>>(B.d_mse, cnt, B.d_s64);
+  k_sum_scan<<<1, 256, 0, stream_>>>(B.d_s64, nch);
+  k_sum_eff<<<wb, kBlock, 0, stream_>>>(B.d_mse, cnt, B.d_s64, B.d_eff, B.d_need);
+  k_sum_pack<<<1, 1024, 0, stream_>>>(B.d_mse, cnt, nch, B.d_need, B.d_list, B.d_fb);
+  HIP_OK(hipMemcpyAsync(B.h_eff, B.d_eff, sizeof(ChunkEff) * 2 * nch, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(B.h_list, B.d_list, sizeof(uint32_t) * (nch + 1), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(B.h_fb, B.d_fb, sizeof(float) * kSumFetch * kSumChunk, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(B.h_mse + np, mm, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+  if (!host_wait_stream(stream_, err)) return false;  // the async lanes go on while the host waits
+  // sampling_strategy.rs:138-141, bit for bit (wpt_seqsum.h)
+  SumFetch F{B.h_list, B.h_fb, B.d_mse, B.h_mse, stream_, (size_t)cnt, 0u, true};
+  const float sum = seq_sum_walk_fetch(cnt, B.h_eff, SumFetch::get, &F, &stats_.sum_resummed);
+  stats_.sum_fetched += F.fetched;
+  stats_.sum_chunks += nch;
+  if (!F.ok) { err = "error sum: chunk copy failed"; return false; }
+  uint32_t keys[2];
+  memcpy(keys, B.h_mse + np, sizeof keys);
+  stats[0] = sum;
+  keys[0] = f_unkey(keys[0]);
+  keys[1] = f_unkey(keys[1]);
+  memcpy(&stats[1], &keys[0], sizeof(float));  // min, max (:142-144)
+  memcpy(&stats[2], &keys[1], sizeof(float));
+  return true;
+}
+
+// A round of screen half h of the W x H frame over pn pixels: samples per
+// pixel into rc, scanned in place to their offsets (rc[pn] = the round's
+// length, also in *h_total, a pinned word), the pixels' counts so far into
+// rbase, the half's sampling view into samp. stats = {mse_sum, mse_min,
+// mse_max} of the half (an estimating round's; else unused).
+bool Renderer::plan_counts(uint32_t W, uint32_t H, uint32_t pn, int h, bool adaptive, bool first, const float stats[3],
+                           const uint32_t* cnt_px, const float* mse_l, const float* mse_r, uint32_t* rc,
+                           uint32_t* rbase, uint32_t* sums, uint8_t* samp, uint32_t* h_total, std::string& err) {
+  RoundParams RP;
+  RP.W = W; RP.H = H; RP.npix = pn; RP.half = W / 2;
+  RP.which = (uint32_t)h;
+  RP.adaptive = adaptive ? 1u : 0u;
+  RP.first = first ? 1u : 0u;
+  for (int k = 0; k < 3; k++) RP.stats[k] = stats[k];
+  k_plan_round<<<blocks_for((uint64_t)pn + 1), kBlock, 0, stream_>>>(RP, nullptr, cnt_px, mse_l, mse_r, rc, rbase, samp);
+  HIP_OK(hipGetLastError());
+  const uint32_t n = pn + 1;
+  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
+  k_scan_local<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
+  k_scan_sums<<<1, kBlock, 0, stream_>>>(sums, nb);
+  k_scan_add<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(h_total, rc + pn, sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+  return host_wait_stream(stream_, err);
+}
+
 bool Renderer::plan_round(int h, std::string& err) {
   struct Tally {
     std::chrono::steady_clock::time_point t0;
@@ -4770,24 +4863,21 @@ bool Renderer::plan_round(int h, std::string& err) {
       rounds_[k].pos = keep[k].pos;
       rounds_[k].idx = keep[k].idx;
     }
-    const uint32_t nb = (std::max(npix, np) + 1 + kScanChunk - 1) / kScanChunk;
-    HIP_OK(hipMalloc(&d_scan_sums_, sizeof(uint32_t) * (nb + 1)));
-    // per half: np errors, then the {min, max} keys k_mse reduces
-    HIP_OK(hipMalloc(&d_mse_[0], sizeof(float) * (np + 2)));
-    HIP_OK(hipMalloc(&d_mse_[1], sizeof(float) * (np + 2)));
-    // per-tile {min, max} keys of k_mse_tiled (a half's tiles)
-    HIP_OK(hipMalloc(&d_bmm_, sizeof(uint32_t) * 2 * ((w_ / kMseTile + 2) * (h_ / kMseTile + 1))));
-    HIP_OK(hipHostMalloc(&h_mse_[0], sizeof(float) * (np + 2)));
-    HIP_OK(hipHostMalloc(&h_mse_[1], sizeof(float) * (np + 2)));
-    const size_t nch = ((size_t)np + kSumChunk - 1) / kSumChunk + 1;
-    HIP_OK(hipMalloc(&d_s64_, sizeof(double) * nch));
-    HIP_OK(hipMalloc(&d_eff_, sizeof(ChunkEff) * 2 * nch));
-    HIP_OK(hipHostMalloc(&h_eff_, sizeof(ChunkEff) * 2 * nch));
-    HIP_OK(hipMalloc(&d_need_, sizeof(uint32_t) * nch));
-    HIP_OK(hipMalloc(&d_list_, sizeof(uint32_t) * (nch + 1)));
-    HIP_OK(hipMalloc(&d_fb_, sizeof(float) * kSumFetch * kSumChunk));
-    HIP_OK(hipHostMalloc(&h_list_, sizeof(uint32_t) * (nch + 1)));
-    HIP_OK(hipHostMalloc(&h_fb_, sizeof(float) * kSumFetch * kSumChunk));
+    const RoundSizes Z = round_sizes(w_, h_, std::max(npix, np));
+    HIP_OK(hipMalloc(&d_scan_sums_, sizeof(uint32_t) * Z.scan_sums));
+    HIP_OK(hipMalloc(&d_mse_[0], sizeof(float) * Z.mse));
+    HIP_OK(hipMalloc(&d_mse_[1], sizeof(float) * Z.mse));
+    HIP_OK(hipMalloc(&d_bmm_, sizeof(uint32_t) * Z.bmm));
+    HIP_OK(hipHostMalloc(&h_mse_[0], sizeof(float) * Z.mse));
+    HIP_OK(hipHostMalloc(&h_mse_[1], sizeof(float) * Z.mse));
+    HIP_OK(hipMalloc(&d_s64_, sizeof(double) * Z.chunks));
+    HIP_OK(hipMalloc(&d_eff_, sizeof(ChunkEff) * 2 * Z.chunks));
+    HIP_OK(hipHostMalloc(&h_eff_, sizeof(ChunkEff) * 2 * Z.chunks));
+    HIP_OK(hipMalloc(&d_need_, sizeof(uint32_t) * Z.chunks));
+    HIP_OK(hipMalloc(&d_list_, sizeof(uint32_t) * (Z.chunks + 1)));
+    HIP_OK(hipMalloc(&d_fb_, sizeof(float) * Z.fetch));
+    HIP_OK(hipHostMalloc(&h_list_, sizeof(uint32_t) * (Z.chunks + 1)));
+    HIP_OK(hipHostMalloc(&h_fb_, sizeof(float) * Z.fetch));
     for (HalfRounds& r : rounds_) {
       HIP_OK(hipMalloc(&r.rc, sizeof(uint32_t) * (npix + 1)));
       HIP_OK(hipMalloc(&r.rbase, sizeof(uint32_t) * (npix + 1)));
@@ -4797,83 +4887,27 @@ bool Renderer::plan_round(int h, std::string& err) {
       }
     }
     if (nranks_ > 1) {
-      const uint32_t gb = (np + 1 + kScanChunk - 1) / kScanChunk;
-      HIP_OK(hipMalloc(&d_gsums_, sizeof(uint32_t) * (gb + 1)));
+      HIP_OK(hipMalloc(&d_gsums_, sizeof(uint32_t) * round_sizes(w_, h_, np).scan_sums));
     }
     round_cap_ = (uint64_t)npix + 1;
   }
   HalfRounds& R = rounds_[h];
-  const uint32_t half = w_ / 2;
-  RoundParams RP;
-  for (int k = 0; k < 3; k++) RP.stats[k] = 0.0f;
+  float stats[3] = {0.0f, 0.0f, 0.0f};
   const bool estimate = adaptive_[h] && R.idx > 0;
   if (estimate && nranks_ > 1 && !exchange_frame(err)) return false;
   if (estimate) {
-    // per-pixel error, min and max on the GPU; mse_sum on the host: the
-    // reference's sequential f32 sum in raster order, in binade segments of
-    // integer increments (wpt_seqsum.h) instead of one dependent add chain
-    const uint32_t x0 = h ? half : 0u, x1 = h ? w_ : half;
-    const uint32_t cnt = (x1 - x0) * h_;
-    uint32_t* mm = reinterpret_cast<uint32_t*>(d_mse_[h] + np);
-    const dim3 tiles((x1 - x0 + kMseTile - 1) / kMseTile, (h_ + kMseTile - 1) / kMseTile);
-    // the errors' sum: chunk effects on the device, walked on the host; the
-    // chunks the walk will likely re-sum come with them (k_sum_pack), any
-    // other one it re-sums is fetched on demand (SumFetch)
-    const uint32_t nch = (cnt + kSumChunk - 1) / kSumChunk;
-    if (cnt) {
-      k_mse_tiled<<<tiles, kBlock, 0, stream_>>>(d_acc_, d_cnt_, w_, h_, x0, x1, d_mse_[h], d_bmm_);
-      k_mm_reduce<<<1, 1024, 0, stream_>>>(d_bmm_, tiles.x * tiles.y, mm);
-      const uint32_t wb = (uint32_t)(((uint64_t)nch * 64u + kBlock - 1) / kBlock);
-      k_sum_chunks<<<wb, kBlock, 0, stream_>>>(d_mse_[h], cnt, d_s64_);
-      k_sum_scan<<<1, 256, 0, stream_>>>(d_s64_, nch);
-      k_sum_eff<<<wb, kBlock, 0, stream_>>>(d_mse_[h], cnt, d_s64_, d_eff_, d_need_);
-      k_sum_pack<<<1, 1024, 0, stream_>>>(d_mse_[h], cnt, nch, d_need_, d_list_, d_fb_);
-      HIP_OK(hipMemcpyAsync(h_eff_, d_eff_, sizeof(ChunkEff) * 2 * nch, hipMemcpyDeviceToHost, stream_));
-      HIP_OK(hipMemcpyAsync(h_list_, d_list_, sizeof(uint32_t) * (nch + 1), hipMemcpyDeviceToHost, stream_));
-      HIP_OK(hipMemcpyAsync(h_fb_, d_fb_, sizeof(float) * kSumFetch * kSumChunk, hipMemcpyDeviceToHost, stream_));
-    }
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h_mse_[h] + np, mm, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-    if (!host_wait_stream(stream_, err)) return false;  // the async lanes go on while the host waits
-    // sampling_strategy.rs:138-141, bit for bit (wpt_seqsum.h)
-    SumFetch F{h_list_, h_fb_, d_mse_[h], h_mse_[h], stream_, (size_t)cnt, 0u, true};
-    const float sum = cnt ? seq_sum_walk_fetch(cnt, h_eff_, SumFetch::get, &F, &stats_.sum_resummed) : 0.0f;
-    stats_.sum_fetched += F.fetched;
-    stats_.sum_chunks += nch;
-    if (!F.ok) { err = "error sum: chunk copy failed"; return false; }
-    uint32_t keys[2];
-    memcpy(keys, h_mse_[h] + np, sizeof keys);
-    RP.stats[0] = sum;
-    keys[0] = f_unkey(keys[0]);
-    keys[1] = f_unkey(keys[1]);
-    memcpy(&RP.stats[1], &keys[0], sizeof(float));  // min, max (:142-144)
-    memcpy(&RP.stats[2], &keys[1], sizeof(float));
+    const ErrorBufs B{d_mse_[h], h_mse_[h], d_bmm_, d_s64_, d_eff_, h_eff_, d_need_, d_list_, h_list_, d_fb_, h_fb_};
+    if (!estimate_errors(d_acc_, d_cnt_, w_, h_, h, B, stats, err)) return false;
   }
-  RP.W = w_; RP.H = h_; RP.half = half;
-  RP.which = (uint32_t)h;
-  RP.adaptive = adaptive_[h] ? 1u : 0u;
-  RP.first = R.idx == 0 ? 1u : 0u;
   // one rank: the round over its pixels (= the frame); several ranks: the
   // global round over the whole frame, sliced per compute chunk (plan_slice)
   const bool global = nranks_ > 1;
-  const uint32_t pn = global ? np : npix;
-  uint32_t* rc = global ? R.gc : R.rc;
-  uint32_t* rbase = global ? R.gbase : R.rbase;
-  uint32_t* sums = global ? d_gsums_ : d_scan_sums_;
-  RP.npix = pn;
-  k_plan_round<<<blocks_for((uint64_t)pn + 1), kBlock, 0, stream_>>>(RP, nullptr, d_cnt_, d_mse_[0], d_mse_[1], rc,
-                                                                     rbase, d_samp_);
-  HIP_OK(hipGetLastError());
-  const uint32_t n = pn + 1;
-  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
-  k_scan_local<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
-  k_scan_sums<<<1, kBlock, 0, stream_>>>(sums, nb);
-  k_scan_add<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
-  HIP_OK(hipGetLastError());
   // (a word of its own: the lanes' pinned counts may still hold the last
   // batch's, read at the next flush_counts)
-  HIP_OK(hipMemcpyAsync(h_word_, rc + pn, sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-  if (!host_wait_stream(stream_, err)) return false;
+  if (!plan_counts(w_, h_, global ? np : npix, h, adaptive_[h], R.idx == 0, stats, d_cnt_, d_mse_[0], d_mse_[1],
+                   global ? R.gc : R.rc, global ? R.gbase : R.rbase, global ? d_gsums_ : d_scan_sums_, d_samp_,
+                   h_word_, err))
+    return false;
   R.total = h_word_[0];
   R.pos = 0;
   R.idx++;
@@ -4922,6 +4956,93 @@ bool Renderer::seq_sum_device(const float* v, uint64_t n, float& out, std::strin
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (!ok) { err = "device sum failed"; return false; }
+  return true;
+}
+
+// The wpt_adaptive_* hooks' buffers: device and pinned allocations freed
+// together.
+namespace {
+struct HookScratch {
+  std::vector<void*> dev, pinned;
+  bool ok = true;
+  template <class T>
+  T* d(size_t n) {
+    void* p = nullptr;
+    ok = ok && hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) == hipSuccess;
+    if (p) dev.push_back(p);
+    return (T*)p;
+  }
+  template <class T>
+  T* h(size_t n) {
+    void* p = nullptr;
+    ok = ok && hipHostMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) == hipSuccess;
+    if (p) pinned.push_back(p);
+    return (T*)p;
+  }
+  ~HookScratch() {
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+  }
+};
+}  // namespace
+
+bool Renderer::adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, int half, float* mse_out,
+                              float* stats3, std::string& err) {
+  // plan_round's estimate on a host frame, in buffers of its own
+  const uint32_t np = W * H;
+  const uint32_t rw = half ? W - W / 2 : W / 2;
+  const RoundSizes Z = round_sizes(W, H, np);
+  HookScratch S;
+  float4* d_acc = S.d<float4>(np);
+  uint32_t* d_cnt = S.d<uint32_t>(np);
+  const ErrorBufs B{S.d<float>(Z.mse),         S.h<float>(Z.mse),        S.d<uint32_t>(Z.bmm),
+                    S.d<double>(Z.chunks),     S.d<ChunkEff>(2 * Z.chunks), S.h<ChunkEff>(2 * Z.chunks),
+                    S.d<uint32_t>(Z.chunks),   S.d<uint32_t>(Z.chunks + 1), S.h<uint32_t>(Z.chunks + 1),
+                    S.d<float>(Z.fetch),       S.h<float>(Z.fetch)};
+  if (!S.ok) { err = "hipMalloc failed (adaptive_error)"; return false; }
+  std::vector<float4> a4(np);
+  for (uint32_t i = 0; i < np; i++) a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
+  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (!estimate_errors(d_acc, d_cnt, W, H, half, B, stats3, err)) return false;
+  if (rw) {
+    HIP_OK(hipMemcpyAsync(mse_out, B.d_mse, sizeof(float) * rw * H, hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+  }
+  return true;
+}
+
+bool Renderer::adaptive_plan(uint32_t W, uint32_t H, int half, bool first, bool adaptive, const float* mse,
+                             const float* stats3, const uint32_t* cnt, uint32_t* count, uint32_t* offset,
+                             uint32_t* base, uint8_t* samp, std::string& err) {
+  // plan_round's planning part on host data, in buffers of its own
+  const uint32_t np = W * H;
+  const uint32_t rw = half ? W - W / 2 : W / 2;
+  const RoundSizes Z = round_sizes(W, H, np);
+  HookScratch S;
+  float* d_mse = S.d<float>(Z.mse);
+  uint32_t* d_cnt = S.d<uint32_t>(np);
+  uint32_t* rc = S.d<uint32_t>((size_t)np + 1);
+  uint32_t* rbase = S.d<uint32_t>((size_t)np + 1);
+  uint32_t* sums = S.d<uint32_t>(Z.scan_sums);
+  uint8_t* d_samp = S.d<uint8_t>((size_t)np * 4);
+  uint32_t* h_total = S.h<uint32_t>(1);
+  if (!S.ok) { err = "hipMalloc failed (adaptive_plan)"; return false; }
+  if (rw) HIP_OK(hipMemcpyAsync(d_mse, mse, sizeof(float) * rw * H, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_samp, samp, (size_t)np * 4, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (!plan_counts(W, H, np, half, adaptive, first, stats3, d_cnt, half ? nullptr : d_mse, half ? d_mse : nullptr, rc,
+                   rbase, sums, d_samp, h_total, err))
+    return false;
+  HIP_OK(hipMemcpyAsync(offset, rc, sizeof(uint32_t) * ((size_t)np + 1), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(base, rbase, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(samp, d_samp, (size_t)np * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (offset[np] != h_total[0]) { err = "adaptive_plan: the round total differs from the last offset"; return false; }
+  // the kernel's counts were scanned in place: they are the offsets' differences
+  for (uint32_t p = 0; p < np; p++) count[p] = offset[p + 1] - offset[p];
   return true;
 }
 

@@ -222,6 +222,43 @@ def photon_sample(points, states, view, table=True):
     return light, pdf, out
 
 
+def adaptive_error(acc, cnt, half):
+    """Test hook: the error estimate of an adaptive round on the frame acc
+    (H, W, 3) f32 sums / cnt (H, W) u32 counts, through the session's planner
+    kernels and host walk: (errors of screen half `half` (H, its width), f32
+    {sum, min, max})."""
+    a = np.ascontiguousarray(acc, dtype=np.float32)
+    c = np.ascontiguousarray(cnt, dtype=np.uint32)
+    H, W = c.shape
+    assert a.shape == (H, W, 3)
+    rw = W - W // 2 if half else W // 2
+    mse = np.empty((H, rw), dtype=np.float32)
+    stats = np.empty(3, dtype=np.float32)
+    _check(lib().wpt_adaptive_error(W, H, a.ctypes.data, c.ctypes.data, int(half), mse.ctypes.data, stats.ctypes.data))
+    return mse, stats
+
+
+def adaptive_plan(width, height, half, mse, stats, cnt, samp, first=False, adaptive=True):
+    """Test hook: the planning part of a round of screen half `half` from the
+    caller's errors, {sum, min, max} and counts: (count (H, W), offset
+    (W*H + 1), base (H, W), the sampling view (H, W, 4) u8; samp is not
+    modified)."""
+    m = np.ascontiguousarray(mse, dtype=np.float32)
+    s = np.ascontiguousarray(stats, dtype=np.float32)
+    c = np.ascontiguousarray(cnt, dtype=np.uint32)
+    view = np.array(samp, dtype=np.uint8, order="C", copy=True)
+    rw = width - width // 2 if half else width // 2
+    assert m.size == height * rw and s.shape == (3,)
+    assert c.size == width * height and view.size == 4 * width * height
+    count = np.empty((height, width), dtype=np.uint32)
+    offset = np.empty(width * height + 1, dtype=np.uint32)
+    base = np.empty((height, width), dtype=np.uint32)
+    _check(lib().wpt_adaptive_plan(width, height, int(half), int(bool(first)), int(bool(adaptive)), m.ctypes.data,
+                                   s.ctypes.data, c.ctypes.data, count.ctypes.data, offset.ctypes.data,
+                                   base.ctypes.data, view.ctypes.data))
+    return count, offset, base, view.reshape(height, width, 4)
+
+
 def read_radiance(width, height):
     acc = np.empty(width * height * 3, dtype=np.float32)
     cnt = np.empty(width * height, dtype=np.uint32)
