@@ -214,7 +214,12 @@ int wpt_copy_partition(void* device_dst);
  * With adaptive halves and several ranks, compute(n) advances the GLOBAL
  * round sequence by n positions (every rank passes the same n) and each rank
  * traces the positions on its own pixels; the union of the partitions is then
- * bitwise the single-rank frame after compute(n). fn = NULL unregisters. */
+ * bitwise the single-rank frame after compute(n). With WPT_OPT_STOCK_RANKS a
+ * rank takes those samples from the sample stock of its partition, traced
+ * ahead of the rounds; the exchanges, one per round of an adaptive half after
+ * its first, are the same calls in the same order on every rank either way,
+ * and refills in flight run across them (they write the ring only).
+ * fn = NULL unregisters. */
 typedef int (*wpt_exchange_fn)(void* user);
 int wpt_set_exchange(wpt_exchange_fn fn, void* user, void* local_dev, void* gathered_dev, uint64_t slot);
 /* float4 entries per rank the exchange needs (the largest partition). */
@@ -228,7 +233,9 @@ int64_t wpt_exchange_slot(void);
  * (wpt_set_partition), plus an RCCL communicator. compute() then traces only
  * the rank's pixels with no communication; with adaptive halves the ranks
  * exchange the frame at round boundaries over the communicator
- * (ncclAllGather), so every rank must pass the same n to compute().
+ * (ncclAllGather), so every rank must pass the same n to compute(). A rank's
+ * sample stock (WPT_OPT_STOCK_RANKS) is its own: the collectives do not
+ * depend on it.
  * wpt_gather_frame(root) (collective): every rank's partition into the root's
  * frame (grouped ncclSend / ncclRecv over xGMI); results() / read_radiance()
  * on the root then return the whole image. */
@@ -372,10 +379,11 @@ int wpt_set_lanes(int32_t n);
 /* 15-19 and 21 (the fast tree's build and drain options) were removed in round 5 */
 #define WPT_OPT_FINISH_EVERY 20  /* RR-only batches: bounces between reads of the live count (a host round trip; default 4) */
 #define WPT_OPT_PROBE 22         /* record the wave timelines of the next N traversal launches (wpt_probe_read; default 0 = off) */
-#define WPT_OPT_STOCK 23         /* adaptive halves (one rank): per-pixel ring of this many samples traced ahead of the rounds
-                                    by refill batches on the async lanes; a round adds its samples from it in sample order
-                                    and traces only what it lacks (0 off, or a power of two 64..4096; default 1024, halved
-                                    while pixels x slots exceed 2^32 or the ring 48 GB) */
+#define WPT_OPT_STOCK 23         /* adaptive halves (one rank; several ranks with WPT_OPT_STOCK_RANKS): a ring of this many
+                                    samples per pixel of the rank's partition, traced ahead of the rounds by refill batches on
+                                    the async lanes; a round adds its samples from it in sample order and traces only what it
+                                    lacks (0 off, or a power of two 64..4096; default 1024, halved while partition pixels x
+                                    slots exceed 2^32 or the ring 48 GB) */
 #define WPT_OPT_STOCK_LANES 24   /* async lanes the refills rotate over, 1..5 (default 2) */
 #define WPT_OPT_FILL 25          /* one random + one adaptive half (the reference's init defaults): the random half's whole
                                     rounds outside its 2 seam columns run on the fill lane beside the adaptive half's
@@ -407,6 +415,15 @@ int wpt_set_lanes(int32_t n);
                                     with k_generate_shade: a primary ray it resolves (WPT_OPT_PRESOLVE) is shaded at once, from
                                     registers, instead of being written to the back of stream 0 and read back by k_shade(0);
                                     0: k_generate_ps and k_shade as before. The frame and every count are the same bits. */
+#define WPT_OPT_STOCK_RANKS 42   /* 1: sessions with several ranks use the sample stock too: every rank keeps a ring over its own
+                                    partition (about 1/N of the one-rank ring) and adds its pixels' share of the global rounds
+                                    from it; 0 (default): they trace each round's samples as the round takes them. Changing it
+                                    within a session drops the stock as a WPT_OPT_STOCK change does. The frame, the counts, the
+                                    sampling view and every ray count are the same bits for both values. */
+#define WPT_OPT_STOCK_RING_BYTES 43 /* read-only: bytes of the two ring blocks (radiance + ray counts, refill ids: 20 per slot) of
+                                       the session's sample stock as it sized them, 0 while it holds none. A session that stops
+                                       using its ring (WPT_OPT_STOCK 0, WPT_OPT_STOCK_RANKS 0, another partition or viewport)
+                                       keeps the blocks, and this value, until it sizes its next ring or ends */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */

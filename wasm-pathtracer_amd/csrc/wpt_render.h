@@ -219,8 +219,8 @@ struct Batch {
   const uint32_t* part = nullptr;
   uint32_t npix = 0;
   // explicit mapping (k_generate): entry p covers positions [moff[p],
-  // moff[p+1]) with samples mbase[p] ..; entry p is pixel mlist[p] (or the
-  // partition pixel p); a stock batch stores its radiance into the ring
+  // moff[p+1]) with samples mbase[p] ..; entry p is partition entry mlist[p]
+  // (or p); a stock batch stores its radiance into the ring
   const uint32_t* moff = nullptr;
   const uint32_t* mbase = nullptr;
   const uint32_t* mlist = nullptr;
@@ -485,10 +485,12 @@ class Renderer {
   uint32_t* h_list_ = nullptr;
   float* h_fb_ = nullptr;
   // The sample stock of adaptive halves (wpt_stock.h, WPT_OPT_STOCK): a ring
-  // of stock_slots_ samples per pixel (radiance + ray counts) and the id of
-  // the refill tracing each, the frontier per pixel, the consumed rays; the
-  // refills in flight (a pool; each one async batch on one stock lane, in
-  // turn); the round's deficit offsets.
+  // of stock_slots_ samples per pixel of this rank's partition (radiance +
+  // ray counts) and the id of the refill tracing each, the frontier per
+  // partition entry, the consumed rays and samples; the refills in flight (a
+  // pool; each one async batch on one stock lane, in turn); the round's
+  // deficit offsets. With several ranks (WPT_OPT_STOCK_RANKS) the rounds are
+  // the global ones every rank plans; a rank stocks its own pixels only.
   uint32_t stock_slots_ = 1024;  // WPT_OPT_STOCK (power of two; 0: off): at most, see stock_alloc
   int stock_lanes_ = 2;         // WPT_OPT_STOCK_LANES: async lanes the refills rotate over
   uint32_t stock_ahead_ = 40;   // WPT_OPT_STOCK_AHEAD: a refill stocks ahead * c + extra samples per pixel
@@ -501,10 +503,11 @@ class Renderer {
   uint32_t* d_stock_id_ = nullptr;
   size_t stock_bytes_[2] = {0, 0};   // the two ring blocks' sizes (cached blocks may be larger)
   uint32_t* d_front_ = nullptr;
-  uint32_t* d_def_ = nullptr;        // [npix + 1] deficit counts -> offsets, then [npix] bases
-  uint32_t* d_bmax_ = nullptr;       // per-block maxima / ray sums scratch
-  unsigned long long* d_rays_ = nullptr;  // [2] consumed rays (extension, shadow), + scratch
-  uint64_t stock_cap_ = 0;           // pixels x slots the ring holds (0: not allocated)
+  uint32_t* d_def_ = nullptr;        // [npart + 1] deficit counts -> offsets, then [npart] bases
+  uint32_t* d_bmax_ = nullptr;       // per-block maxima scratch
+  unsigned long long* d_rays_ = nullptr;  // [3] consumed rays (extension, shadow) and samples, [1] unused, + scratch
+  uint64_t stock_cap_ = 0;           // partition pixels x slots the ring holds (0: not allocated)
+  uint64_t stock_frame_ = 0;         // the viewport's pixels when the ring was made (a resize orphans it)
   uint32_t stock_used_slots_ = 0;
   static constexpr int kMaxRefill = 8;
   static constexpr uint64_t kStockBytes = 48ull << 30;  // the ring's HBM at most (1080p: 1024 slots, 42 GB)
@@ -526,7 +529,26 @@ class Renderer {
   uint32_t round_need_[2] = {0, 0};   // per half: 1 + the refill its current round's samples wait for (0: none)
   bool stock_redo_[2] = {false, false};  // per half: the stock was dropped while its round was partly added
   int log_ = 0;  // WPT_OPT_LOG: host steps of the adaptive rounds and async lanes to stderr (debugging)
-  bool stock_active(int h) const { return stock_slots_ != 0 && nranks_ == 1 && adaptive_[h]; }
+  // WPT_OPT_STOCK_RANKS: sessions with several ranks use the stock. Off by
+  // default: the only measurement so far, two ranks sharing one card, read
+  // 892-976 Mray/s with it and 751-955 without, ranges that overlap
+  // (profiles/stockranks/README.md)
+  bool stock_ranks_ = false;
+  // half h's rounds take their samples from the stock; with several ranks a
+  // rank that owns no pixel of the half has nothing to stock
+  bool stock_active(int h) const {
+    return stock_slots_ != 0 && adaptive_[h] && (nranks_ == 1 || (stock_ranks_ && half_npix_[h] != 0));
+  }
+  // the session runs async lanes (refills, the filler) beside its main lanes
+  bool async_lanes() const {
+    return ((stock_slots_ && (nranks_ == 1 || stock_ranks_)) || (fill_on_ && nranks_ == 1)) &&
+           (adaptive_[0] || adaptive_[1]);
+  }
+  // WPT_OPT_STOCK_RING_BYTES: the ring's two blocks (float4 + refill id per
+  // slot) as the session sized them; a cached block reused for one may be
+  // larger. A ring the session stopped using (the stock switched off, another
+  // partition) is held, and counted, until the next ring is sized
+  uint64_t ring_bytes() const { return d_stock_ ? stock_cap_ * (sizeof(float4) + sizeof(uint32_t)) : 0; }
   bool stock_alloc(std::string& err);
   void stock_drop();                     // forget the ring (reset, reallocation)
   bool stock_round(int h, uint64_t left, std::string& err);   // after half h's round is planned: deficit + refill
@@ -664,7 +686,9 @@ class Renderer {
   uint32_t rank_ = 0, nranks_ = 1, tile_ = 16;
   std::vector<uint32_t> part_pix_;
   uint32_t* d_part_pix_ = nullptr;
-  uint32_t* d_half_pix_[2] = {nullptr, nullptr};  // one rank: each screen half's pixels, tile order
+  // each screen half's pixels of this rank: one rank in tile order; several
+  // ranks as partition entries (indices into part_pix_) in partition order
+  uint32_t* d_half_pix_[2] = {nullptr, nullptr};
   uint32_t* d_frame_pix_ = nullptr;                // one rank: the frame's pixels, tile order
   uint32_t half_npix_[2] = {0, 0};
   uint64_t next_path_ = 0;

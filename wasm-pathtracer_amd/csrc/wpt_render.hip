@@ -871,10 +871,12 @@ struct GenParams {
 // Path k of the progressive order: pixel k mod P, sample k div P; or, with
 // rnd_off (a sample round, wpt_adaptive.h, or a stock batch, wpt_stock.h),
 // the entry p whose consecutive range [rnd_off[p], rnd_off[p+1]) holds k,
-// sample rnd_base[p] + k - rnd_off[p]; entry p is pixel rnd_list[p] when
-// given (a stock refill over a half's pixel list), else partition pixel p.
+// sample rnd_base[p] + k - rnd_off[p]; entry p is partition entry
+// rnd_list[p] when given (a stock refill over the rank's pixels of a half),
+// else partition entry p. row: the path's partition entry (its row of the
+// sample stock's ring, wpt_stock.h), pixel: that entry's frame pixel.
 struct GenPath {
-  uint32_t pl, sample, pixel, s, type;
+  uint32_t pl, sample, row, pixel, s, type;
   V3 v;
 };
 __device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* __restrict__ part_pix, uint64_t k,
@@ -895,7 +897,8 @@ __device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* 
     g.pl = (uint32_t)(k % P.npix);
     g.sample = (uint32_t)(k / P.npix);
   }
-  g.pixel = rnd_list ? rnd_list[g.pl] : part_pix ? part_pix[g.pl] : g.pl;
+  g.row = rnd_list ? rnd_list[g.pl] : g.pl;
+  g.pixel = part_pix ? part_pix[g.row] : g.row;
   const uint32_t x = g.pixel % P.W, y = g.pixel / P.W;
   uint32_t s = path_seed(P.seed, g.pixel, g.sample);
   const float fx = (((float)x + xs_next(s)) * P.w_inv - 0.5f) * P.ar;
@@ -911,9 +914,9 @@ __device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* 
 
 // Where path g's radiance is accumulated (pix_out): its pixel, or the entry of
 // a sample round's list (rnd_off); a stock batch (stock_slots != 0) writes the
-// path's stock slot, pixel x slots + sample mod slots, instead.
+// path's stock slot, ring row x slots + sample mod slots, instead.
 __device__ __forceinline__ uint32_t path_slot(const GenPath& g, const uint32_t* rnd_off, uint32_t stock_slots) {
-  return stock_slots ? g.pixel * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
+  return stock_slots ? g.row * stock_slots + (g.sample & (stock_slots - 1u)) : rnd_off ? g.pl : g.pixel;
 }
 
 // A miss of a path with throughput thr adds nothing to its colour: throughput *
@@ -2981,6 +2984,13 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
       stock_drop();
       stock_slots_ = (uint32_t)v;
       return true;
+    case 42:
+      // several ranks with the stock: the ring and the lanes change with it
+      if (!range(0, 1)) return false;
+      if (!drain_async(err)) return false;
+      stock_drop();
+      stock_ranks_ = v != 0;
+      return true;
     case 25: if (!range(0, 1)) return false; fill_on_ = v != 0; return true;
     case 30: if (!range(0, 64)) return false; stock_ahead_ = (uint32_t)v; return true;
     case 32: if (!range(1, 1024)) return false; stock_every_ = (uint32_t)v; return true;
@@ -3001,7 +3011,8 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 27: if (!range(0, 100)) return false; async_grid_pct_ = (int)v; return true;
     case 28:
     case 29:
-    case 41: err = "read-only option"; return false;
+    case 41:
+    case 43: err = "read-only option"; return false;
     case 24:
       if (!range(1, kMaxLanes - kAsyncLane0 - 1)) return false;  // the fill lane follows them
       if (!drain_async(err)) return false;
@@ -3061,6 +3072,8 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     // array and CDFs in LDS; -1 no tree
     case 41: v = !photons_ok_ ? -1 : ds_.oct_lds_words == 0 ? 0 : (ds_.oct_lds_words > ds_.oct_nodes ? 2 : 1); return true;
     case 24: v = stock_lanes_; return true;
+    case 42: v = stock_ranks_ ? 1 : 0; return true;
+    case 43: v = (int64_t)ring_bytes(); return true;
     default: return false;
   }
 }
@@ -3125,6 +3138,19 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
     if (!xidx.empty()) {
       HIP_OK(hipMalloc(&d_xidx_, sizeof(uint32_t) * xidx.size()));
       HIP_OK(hipMemcpy(d_xidx_, xidx.data(), sizeof(uint32_t) * xidx.size(), hipMemcpyHostToDevice));
+    }
+    // each screen half's own pixels as partition entries, in partition order
+    // (the sample stock's refills walk them; a rank may own none of a half)
+    const uint32_t half = w_ / 2;
+    for (int hh = 0; hh < 2; hh++) {
+      std::vector<uint32_t> rows;
+      for (size_t i = 0; i < part_pix_.size(); i++)
+        if ((part_pix_[i] % w_ >= half) == (hh == 1)) rows.push_back((uint32_t)i);
+      half_npix_[hh] = (uint32_t)rows.size();
+      if (!rows.empty()) {
+        HIP_OK(hipMalloc(&d_half_pix_[hh], sizeof(uint32_t) * rows.size()));
+        HIP_OK(hipMemcpy(d_half_pix_[hh], rows.data(), sizeof(uint32_t) * rows.size(), hipMemcpyHostToDevice));
+      }
     }
   } else if (w_ && h_) {
     part_pix_.resize((size_t)w_ * h_);
@@ -3294,11 +3320,9 @@ uint64_t Renderer::batch_cap() const {
 }
 
 // Lanes a main batch may use: all of them, or those below the async lanes
-// while speculated batches may run there (an adaptive session on one rank).
-int Renderer::main_lanes() const {
-  const bool async = (stock_slots_ || fill_on_) && nranks_ == 1 && (adaptive_[0] || adaptive_[1]);
-  return async ? std::min(nlanes_, kAsyncLane0) : nlanes_;
-}
+// while speculated batches may run there (an adaptive session on one rank, or
+// on several with WPT_OPT_STOCK_RANKS).
+int Renderer::main_lanes() const { return async_lanes() ? std::min(nlanes_, kAsyncLane0) : nlanes_; }
 
 // One lane's count words of a finished batch into st: the rays of bounces
 // 0 .. b-1 (bounce 0: k_generate's count, bounce i: the append counter of
@@ -3763,16 +3787,16 @@ LaunchCtx Renderer::lane0_ctx(bool count) const {
 // The adaptive halves' sample stock (wpt_stock.h)
 // ---------------------------------------------------------------------------
 
-// The ring for this viewport (pixels x slots radiance + ray counts, and the
-// refill id of each slot), the frontier (= the counts: an empty ring), the
-// round deficit and reduction scratch, the refill pool.
+// The ring for this rank's partition (pixels x slots radiance + ray counts,
+// and the refill id of each slot), the frontier (= the counts: an empty
+// ring), the round deficit and reduction scratch, the refill pool.
 bool Renderer::stock_alloc(std::string& err) {
-  const uint64_t np = (uint64_t)w_ * h_;
+  const uint64_t np = part_pix_.size();
   // WPT_OPT_STOCK slots, fewer for large viewports: slot indices stay below
   // 2^32 and the ring (20 B per slot) below kStockBytes
   uint32_t slots = stock_slots_;
   while (slots > 64 && (np * slots > 0xFFFFFFFFull || np * slots * 20 > kStockBytes)) slots >>= 1;
-  if (d_stock_ && stock_cap_ == np * slots && stock_used_slots_ == slots) return true;
+  if (d_stock_ && stock_cap_ == np * slots && stock_frame_ == (uint64_t)w_ * h_ && stock_used_slots_ == slots) return true;
   if (np * slots > 0xFFFFFFFFull) { err = "stock: viewport too large for the sample stock (WPT_OPT_STOCK 0)"; return false; }
   // every lane done with the old ring: the async lanes, and the main stream
   // (which waits on the main lanes' last batch: its k_stock_store)
@@ -3799,9 +3823,10 @@ bool Renderer::stock_alloc(std::string& err) {
   HIP_OK(hipMalloc(&d_front_, sizeof(uint32_t) * np));
   HIP_OK(hipMalloc(&d_def_, sizeof(uint32_t) * (2 * np + 2)));
   HIP_OK(hipMalloc(&d_bmax_, sizeof(uint32_t) * nb + 16));
-  HIP_OK(hipMalloc(&d_rays_, sizeof(unsigned long long) * (2 + 2 * nb)));
-  HIP_OK(hipMemsetAsync(d_rays_, 0, sizeof(unsigned long long) * 2, stream_));
-  HIP_OK(hipMemcpyAsync(d_front_, d_cnt_, sizeof(uint32_t) * np, hipMemcpyDeviceToDevice, stream_));
+  HIP_OK(hipMalloc(&d_rays_, sizeof(unsigned long long) * (4 + 3 * nb)));
+  HIP_OK(hipMemsetAsync(d_rays_, 0, sizeof(unsigned long long) * 4, stream_));
+  k_front_init<<<blocks_for(np), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, (uint32_t)np, d_cnt_, d_front_);
+  HIP_OK(hipGetLastError());
   for (Refill& f : refills_) {
     HIP_OK(hipMalloc(&f.off, sizeof(uint32_t) * (np + 1)));
     HIP_OK(hipMalloc(&f.base, sizeof(uint32_t) * (np + 1)));
@@ -3812,6 +3837,7 @@ bool Renderer::stock_alloc(std::string& err) {
       for (hipEvent_t& e : re) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   stock_cap_ = np * slots;
+  stock_frame_ = (uint64_t)w_ * h_;
   stock_used_slots_ = slots;
   round_need_[0] = round_need_[1] = 0;
   return true;
@@ -3829,8 +3855,13 @@ void Renderer::stock_drop() {
     f.live = false;
   }
   round_need_[0] = round_need_[1] = 0;
-  if (d_front_ && d_cnt_ && stock_cap_ == (uint64_t)w_ * h_ * stock_used_slots_)
-    (void)hipMemcpyAsync(d_front_, d_cnt_, sizeof(uint32_t) * (size_t)w_ * h_, hipMemcpyDeviceToDevice, stream_);
+  // (only while the ring still belongs to this viewport and partition: during
+  // a resize the partition list is the old viewport's and the counts are the
+  // new one's; the next stock_alloc then makes a new ring and frontier)
+  const uint64_t np = part_pix_.size();
+  if (d_front_ && d_cnt_ && np && stock_frame_ == (uint64_t)w_ * h_ && stock_cap_ == np * stock_used_slots_ &&
+      (nranks_ == 1 || d_part_pix_))
+    k_front_init<<<blocks_for(np), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, (uint32_t)np, d_cnt_, d_front_);
 }
 
 // After half h's round is planned: its deficit (pixels whose stock lacks
@@ -3856,8 +3887,11 @@ bool Renderer::stock_round(int h, uint64_t left, std::string& err) {
   uint32_t* bmax = d_bmax_;
   uint32_t* need = d_bmax_ + nb;
   stock_redo_[h] = false;
-  k_stock_plan<<<nb, kBlock, 0, stream_>>>(npix, R.rc, R.rbase, d_cnt_, d_front_, d_stock_id_, slots, def_cnt, def_base,
-                                           bmax);
+  // several ranks: the global round's offsets and bases, per frame pixel
+  const bool global = nranks_ > 1;
+  k_stock_plan<<<nb, kBlock, 0, stream_>>>(global ? d_part_pix_ : nullptr, npix, global ? R.gc : R.rc,
+                                           global ? R.gbase : R.rbase, d_cnt_, d_front_, d_stock_id_, slots, def_cnt,
+                                           def_base, bmax);
   k_max_reduce<<<1, 1024, 0, stream_>>>(bmax, nb, need);
   auto scan = [&](uint32_t* a, uint32_t n) {
     const uint32_t sb = (n + kScanChunk - 1) / kScanChunk;
@@ -3903,9 +3937,12 @@ bool Renderer::stock_round(int h, uint64_t left, std::string& err) {
 }
 
 // q (of 1024) scaling a refill of half h with lookahead `ahead` to the
-// `after` positions the call still gives the half's later rounds.
+// `after` positions the call still gives the half's later rounds. The round's
+// total and `after` count positions of the whole frame's half (with several
+// ranks too), so the extra samples are those of all its pixels.
 uint32_t Renderer::refill_scale(int h, uint32_t ahead, uint64_t after) const {
-  const uint64_t expect = (uint64_t)ahead * rounds_[h].total + (uint64_t)stock_extra_ * half_npix_[h];
+  const uint64_t half_px = (uint64_t)(h ? w_ - w_ / 2 : w_ / 2) * h_;
+  const uint64_t expect = (uint64_t)ahead * rounds_[h].total + (uint64_t)stock_extra_ * half_px;
   return expect <= after ? 1024u : (uint32_t)(after * 1024 / std::max<uint64_t>(expect, 1));
 }
 
@@ -3925,9 +3962,10 @@ Renderer::Refill* Renderer::refill_slot(std::string& err) {
 // counts of the half's current round (c per pixel: the predictor).
 void Renderer::refill_plan(Refill& F, int h, uint32_t ahead, uint32_t q) {
   const uint32_t nh = half_npix_[h];
-  k_refill_plan<<<blocks_for((uint64_t)nh + 1), kBlock, 0, stream_>>>(d_half_pix_[h], nh, rounds_[h].rc, d_cnt_,
-                                                                      d_front_, d_stock_id_, stock_used_slots_, ahead,
-                                                                      stock_extra_, q, refill_id_, F.off, F.base);
+  const bool global = nranks_ > 1;
+  k_refill_plan<<<blocks_for((uint64_t)nh + 1), kBlock, 0, stream_>>>(
+      global ? d_part_pix_ : nullptr, d_half_pix_[h], nh, global ? rounds_[h].gc : rounds_[h].rc, d_cnt_, d_front_,
+      d_stock_id_, stock_used_slots_, ahead, stock_extra_, q, refill_id_, F.off, F.base);
   const uint32_t n = nh + 1, sb = (n + kScanChunk - 1) / kScanChunk;
   k_scan_local<<<sb, kBlock, 0, stream_>>>(F.off, n, d_scan_sums_);
   k_scan_sums<<<1, kBlock, 0, stream_>>>(d_scan_sums_, sb);
@@ -4033,11 +4071,14 @@ bool Renderer::stock_consume(int h, uint64_t a, uint64_t b, std::string& err) {
   const uint32_t npix = (uint32_t)part_pix_.size();
   const uint32_t nb = blocks_for(npix);
   if (log_) WPT_LOGF("consume h=%d [%lu, %lu) need=%u\n", h, (unsigned long)a, (unsigned long)b, need);
-  k_consume<<<nb, kBlock, 0, stream_>>>(npix, R.rc, R.rbase, (uint32_t)a, (uint32_t)b, d_stock_, stock_used_slots_,
-                                         d_acc_, d_cnt_, d_rays_ + 2);
-  k_rays_reduce<<<1, 1024, 0, stream_>>>(d_rays_ + 2, nb, d_rays_);
+  // (the samples added, this rank's share of b - a, come back with the rays:
+  // stock_flush)
+  const bool global = nranks_ > 1;
+  k_consume<<<nb, kBlock, 0, stream_>>>(global ? d_part_pix_ : nullptr, npix, global ? R.gc : R.rc,
+                                         global ? R.gbase : R.rbase, (uint32_t)a, (uint32_t)b, d_stock_,
+                                         stock_used_slots_, d_acc_, d_cnt_, d_rays_ + 4);
+  k_rays_reduce<<<1, 1024, 0, stream_>>>(d_rays_ + 4, nb, d_rays_);
   HIP_OK(hipGetLastError());
-  stats_.stock_consumed += b - a;
   return true;
 }
 
@@ -4062,19 +4103,21 @@ bool Renderer::refill_count(Refill& f, bool block, std::string& err) {
   return true;
 }
 
-// The rays of the samples the rounds took (k_consume) into stats_, and the
+// The samples the rounds took (k_consume) and their rays into stats_, and the
 // counts of the refills done by now.
 bool Renderer::stock_flush(std::string& err) {
   for (Refill& f : refills_)
     if (f.live && !refill_count(f, false, err)) return false;
   if (!d_rays_) return true;
-  unsigned long long r[2];
+  unsigned long long r[3];
   HIP_OK(hipMemcpyAsync(r, d_rays_, sizeof r, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipMemsetAsync(d_rays_, 0, sizeof r, stream_));
   if (!host_wait_stream(stream_, err)) return false;
   stats_.rays += r[0];
   stats_.shadow_rays += r[1];
   stats_.stock_rays_used += r[0] + r[1];
+  stats_.paths += r[2];
+  stats_.stock_consumed += r[2];
   return true;
 }
 
@@ -4267,9 +4310,16 @@ bool Renderer::compute_half(int h, uint64_t n, std::string& err) {
     if (R.pos == R.total && (!plan_round(h, err) || (stock_active(h) && !stock_round(h, n - done, err)))) return false;
     if (nranks_ > 1) {
       const uint64_t m = std::min(std::min(bsz, n - done), R.total - R.pos);
-      uint64_t local = 0;
-      if (!plan_slice(h, R.pos, R.pos + m, local, err)) return false;
-      if (local && !run_batch(0, local, h, err)) return false;
+      if (stock_active(h)) {
+        // positions [pos, pos + m) of the global round: this rank's pixels
+        // add theirs from its ring (as on one rank, below)
+        if (stock_redo_[h] && !stock_round(h, n - done + R.pos, err)) return false;
+        if (!stock_consume(h, R.pos, R.pos + m, err)) return false;
+      } else {
+        uint64_t local = 0;
+        if (!plan_slice(h, R.pos, R.pos + m, local, err)) return false;
+        if (local && !run_batch(0, local, h, err)) return false;
+      }
       R.pos += m;
       done += m;
     } else {
@@ -4280,7 +4330,6 @@ bool Renderer::compute_half(int h, uint64_t n, std::string& err) {
         // after the stock was dropped)
         if (stock_redo_[h] && !stock_round(h, n - done + R.pos, err)) return false;
         if (!stock_consume(h, R.pos, R.pos + m, err)) return false;
-        stats_.paths += m;
       } else if (!run_batch(R.pos, m, h, err)) {
         return false;
       }

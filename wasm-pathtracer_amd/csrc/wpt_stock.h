@@ -13,20 +13,41 @@
 //
 // Per pixel: cnt (samples accumulated) and front (the next sample index to
 // trace); samples [cnt, front) are in the ring, done or in flight, and
-// front - cnt <= slots. Sample s of pixel p lives at p * slots + s % slots.
-// stock_id[slot] = the refill tracing that sample (a round waits for the
-// latest refill holding one of its samples). One rank: partition pixel = pixel.
+// front - cnt <= slots. stock_id[slot] = the refill tracing that sample (a
+// round waits for the latest refill holding one of its samples).
+//
+// The ring is the rank's own: one row per pixel of its partition, in partition
+// order (npart x slots entries, about 1/N of the frame's with N ranks). Sample
+// s of partition entry p lives at p * slots + s % slots; front, the deficit
+// scratch and the refills' offsets are indexed by p as well. A round's plan
+// (off / base), acc and cnt are indexed by the frame pixel part[p]: with
+// several ranks every rank plans the same global round over the frame. One
+// rank: part = nullptr, entry p is pixel p.
 #pragma once
+
+// Partition entry p's frame pixel.
+__device__ __forceinline__ uint32_t stock_pixel(const uint32_t* __restrict__ part, uint32_t p) {
+  return part ? part[p] : p;
+}
+
+// An empty ring: entry p's frontier = its pixel's count.
+__global__ void __launch_bounds__(kBlock) k_front_init(const uint32_t* __restrict__ part, uint32_t npart,
+                                                       const uint32_t* __restrict__ cnt, uint32_t* __restrict__ front) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p < npart) front[p] = cnt[stock_pixel(part, p)];
+}
 
 // After a round is planned (off: its offsets per pixel; base: the samples
 // each pixel had before it; cnt: the samples it has now, = base unless the
-// round is partly added already, after a dropped stock): of its c = base +
-// (off[p+1] - off[p]) - cnt samples still to add, the deficit d = max(0, c -
+// round is partly added already, after a dropped stock), for every entry p
+// of the partition (pixel x = part[p]): of its c = base[x] + (off[x+1] -
+// off[x]) - cnt[x] samples still to add, the deficit d = max(0, c -
 // (front - cnt)), samples front .. front + d - 1, traced by the round itself
 // (def_base = front; front += d); bmax[block] = 1 + the latest refill id
 // holding the round's other samples (0: none). def_cnt[npix] = 0 is the scan
 // sentinel.
-__global__ void __launch_bounds__(kBlock) k_stock_plan(uint32_t npix, const uint32_t* __restrict__ off,
+__global__ void __launch_bounds__(kBlock) k_stock_plan(const uint32_t* __restrict__ part, uint32_t npix,
+                                                       const uint32_t* __restrict__ off,
                                                        const uint32_t* __restrict__ base,
                                                        const uint32_t* __restrict__ cnt, uint32_t* __restrict__ front,
                                                        const uint32_t* __restrict__ stock_id, uint32_t slots,
@@ -37,9 +58,10 @@ __global__ void __launch_bounds__(kBlock) k_stock_plan(uint32_t npix, const uint
   if (p < npix) {
     // the round's own pixels only (the other half's have c = 0 and may have
     // gained samples since this half's plan)
-    const uint32_t cr = off[p + 1] - off[p];
-    const uint32_t n0 = cnt[p];
-    const uint32_t c = cr ? base[p] + cr - n0 : 0u;
+    const uint32_t x = stock_pixel(part, p);
+    const uint32_t cr = off[x + 1] - off[x];
+    const uint32_t n0 = cnt[x];
+    const uint32_t c = cr ? base[x] + cr - n0 : 0u;
     uint32_t d = 0;
     if (c) {
       const uint32_t f = front[p];
@@ -79,13 +101,16 @@ __global__ void __launch_bounds__(1024) k_max_reduce(const uint32_t* __restrict_
 }
 
 // A refill, planned after a round (before that round's samples are added):
-// pixel list[i] of the half is stocked up to cnt + c + min((ahead * c +
-// extra) * q / 1024, slots - c) samples, at most cnt + slots (the ring: the
-// round still reads [cnt, cnt + c)); q <= 1024 scales the stock down to the
-// positions left in the compute call. Samples front .. front + w - 1
-// (rf_base = front, rf_cnt = w) are marked as this refill's (stock_id =
-// id); front += w.
-__global__ void __launch_bounds__(kBlock) k_refill_plan(const uint32_t* __restrict__ list, uint32_t n,
+// partition entry list[i] (the rank's pixels of the half, in partition
+// order), whose pixel takes c samples in that round (off: the round's offsets
+// per pixel; c predicts the next rounds), is stocked up to cnt + c +
+// min((ahead * c + extra) * q / 1024, slots - c) samples, at most cnt + slots
+// (the ring: the round still reads [cnt, cnt + c)); q <= 1024 scales the
+// stock down to the positions left in the compute call. Samples front ..
+// front + w - 1 (rf_base = front, rf_cnt = w) are marked as this refill's
+// (stock_id = id); front += w.
+__global__ void __launch_bounds__(kBlock) k_refill_plan(const uint32_t* __restrict__ part,
+                                                        const uint32_t* __restrict__ list, uint32_t n,
                                                         const uint32_t* __restrict__ off,
                                                         const uint32_t* __restrict__ cnt, uint32_t* __restrict__ front,
                                                         uint32_t* __restrict__ stock_id, uint32_t slots, uint32_t ahead,
@@ -97,8 +122,9 @@ __global__ void __launch_bounds__(kBlock) k_refill_plan(const uint32_t* __restri
     return;
   }
   const uint32_t p = list[i];
-  const uint32_t c = off[p + 1] - off[p];
-  const uint32_t n0 = cnt[p], f = front[p];
+  const uint32_t x = stock_pixel(part, p);
+  const uint32_t c = off[x + 1] - off[x];
+  const uint32_t n0 = cnt[x], f = front[p];
   const uint32_t room = slots > c ? slots - c : 0u;
   const uint64_t want = (uint64_t)n0 + c + min((((uint64_t)ahead * c + extra) * q) >> 10, (uint64_t)room);
   const uint64_t t = min(want, (uint64_t)n0 + slots);
@@ -117,24 +143,29 @@ __global__ void __launch_bounds__(kBlock) k_stock_store(const uint32_t* __restri
 }
 
 // Positions [a, b) of a round (off / base: its offsets and the samples each
-// pixel had before it): every pixel adds its samples of the range from the
-// ring in sample order (RenderTarget::write, render_target.rs:55-58); the
-// consumed samples' rays (col.w of their paths: extension | shadow << 16)
-// into per-block partial sums rb[2 * block ..], folded by k_rays_reduce.
-__global__ void __launch_bounds__(kBlock) k_consume(uint32_t npix, const uint32_t* __restrict__ off,
+// pixel had before it; with several ranks the global round's): every pixel
+// of the partition adds its samples of the range from its ring row in sample
+// order (RenderTarget::write, render_target.rs:55-58); the consumed samples'
+// rays (col.w of their paths: extension | shadow << 16) and their number
+// (the rank's share of b - a) into per-block partial sums rb[3 * block ..],
+// folded by k_rays_reduce.
+__global__ void __launch_bounds__(kBlock) k_consume(const uint32_t* __restrict__ part, uint32_t npix,
+                                                    const uint32_t* __restrict__ off,
                                                     const uint32_t* __restrict__ base, uint32_t a, uint32_t b,
                                                     const float4* __restrict__ stock, uint32_t slots,
                                                     float4* __restrict__ acc, uint32_t* __restrict__ cnt,
                                                     unsigned long long* __restrict__ rb) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  unsigned long long re = 0, rs = 0;
+  unsigned long long re = 0, rs = 0, ns = 0;
   if (p < npix) {
-    const uint32_t p0 = off[p], p1 = off[p + 1];
+    const uint32_t x = stock_pixel(part, p);
+    const uint32_t p0 = off[x], p1 = off[x + 1];
     const uint32_t o0 = max(a, p0), o1 = min(b, p1);
     if (o1 > o0) {
-      float4 A = acc[p];
-      uint32_t c = cnt[p];
-      const uint32_t s0 = base[p] + (o0 - p0);
+      float4 A = acc[x];
+      uint32_t c = cnt[x];
+      const uint32_t s0 = base[x] + (o0 - p0);
+      ns = o1 - o0;
       for (uint32_t s = s0; s != s0 + (o1 - o0); s++) {
         const float4 v = stock[(size_t)p * slots + (s & (slots - 1u))];
         A.x += v.x;
@@ -145,55 +176,64 @@ __global__ void __launch_bounds__(kBlock) k_consume(uint32_t npix, const uint32_
         re += r & 0xFFFFu;
         rs += r >> 16;
       }
-      acc[p] = A;
-      cnt[p] = c;
+      acc[x] = A;
+      cnt[x] = c;
     }
   }
   for (int o = 32; o > 0; o >>= 1) {
     re += __shfl_xor(re, o, 64);
     rs += __shfl_xor(rs, o, 64);
+    ns += __shfl_xor(ns, o, 64);
   }
-  __shared__ unsigned long long s_r[2][kBlock / 64];
+  __shared__ unsigned long long s_r[3][kBlock / 64];
   if ((threadIdx.x & 63u) == 0) {
     s_r[0][threadIdx.x >> 6] = re;
     s_r[1][threadIdx.x >> 6] = rs;
+    s_r[2][threadIdx.x >> 6] = ns;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (uint32_t w = 1; w < kBlock / 64; w++) {
       re += s_r[0][w];
       rs += s_r[1][w];
+      ns += s_r[2][w];
     }
-    rb[2 * blockIdx.x] = re;
-    rb[2 * blockIdx.x + 1] = rs;
+    rb[3 * blockIdx.x] = re;
+    rb[3 * blockIdx.x + 1] = rs;
+    rb[3 * blockIdx.x + 2] = ns;
   }
 }
 
-// Adds k_consume's per-block ray sums into total[0..1] (the running count
-// of consumed rays, read and cleared by the host).
+// Adds k_consume's per-block sums into total[0..2] (the running counts of
+// consumed rays and samples, read and cleared by the host).
 __global__ void __launch_bounds__(1024) k_rays_reduce(const unsigned long long* __restrict__ rb, uint32_t nb,
                                                       unsigned long long* __restrict__ total) {
-  unsigned long long re = 0, rs = 0;
+  unsigned long long re = 0, rs = 0, ns = 0;
   for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) {
-    re += rb[2 * i];
-    rs += rb[2 * i + 1];
+    re += rb[3 * i];
+    rs += rb[3 * i + 1];
+    ns += rb[3 * i + 2];
   }
   for (int o = 32; o > 0; o >>= 1) {
     re += __shfl_xor(re, o, 64);
     rs += __shfl_xor(rs, o, 64);
+    ns += __shfl_xor(ns, o, 64);
   }
-  __shared__ unsigned long long s_r[2][16];
+  __shared__ unsigned long long s_r[3][16];
   if ((threadIdx.x & 63u) == 0) {
     s_r[0][threadIdx.x >> 6] = re;
     s_r[1][threadIdx.x >> 6] = rs;
+    s_r[2][threadIdx.x >> 6] = ns;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (uint32_t w = 1; w < blockDim.x / 64; w++) {
       re += s_r[0][w];
       rs += s_r[1][w];
+      ns += s_r[2][w];
     }
     total[0] += re;
     total[1] += rs;
+    total[2] += ns;
   }
 }

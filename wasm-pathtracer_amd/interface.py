@@ -356,7 +356,8 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "fill": 25, "async_prio": 26, "async_grid_pct": 27, "scene_traversal": 28, "scene_tri_only": 29,
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
-           "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41}
+           "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41,
+           "stock_ranks": 42, "stock_ring_bytes": 43}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
