@@ -424,6 +424,7 @@ int wpt_set_lanes(int32_t n);
                                        the session's sample stock as it sized them, 0 while it holds none. A session that stops
                                        using its ring (WPT_OPT_STOCK 0, WPT_OPT_STOCK_RANKS 0, another partition or viewport)
                                        keeps the blocks, and this value, until it sizes its next ring or ends */
+#define WPT_OPT_VIEWPORT 44      /* read-only: the session's viewport, width | height << 32 (the size of wpt_first_hit's planes) */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -462,6 +463,28 @@ int wpt_bvh_depth(void);
  * (Scene::shadow_ray, scene.rs:104-133) for {p.xyz, q.xyz} and light shape ids. */
 int wpt_trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out);
 int wpt_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occluded);
+/* First-hit feature planes of sample `sample` of every frame pixel (raster order,
+ * width*height entries each; any pointer may be NULL = not wanted):
+ *  dir3    3 f32  the primary ray's direction (origin = the camera)
+ *  t       f32    Scene::trace distance, +inf on a miss      (trace_original_depth, tracer.rs:205-213)
+ *  id      i32    shape id in the scene's reordered shape list, -1 on a miss
+ *  visits  u32    the reference's num_bvh_hits of this ray   (trace_original_bvh, tracer.rs:216-219)
+ *  normal3 3 f32  Hit.normal (faces the ray); +0 on a miss
+ *  albedo3 3 f32  Diffuse colour, or the Emissive intensity; +0 on a miss
+ *  kind    u8     0 miss, 1 diffuse, 2 emissive
+ * The ray is the one wpt_compute traces first for that pixel and sample, and
+ * the hit is found by the exact BVH2 on every scene. The whole frame on the
+ * calling rank, whatever the partition; the session (accumulation, rounds,
+ * sample stock, wpt_stats, wpt_kernel_times) is not touched. With every
+ * pointer NULL nothing is launched. WPT_ERR_DEVICE if the traversal stack
+ * overflowed (no ray is dropped silently). u8 colour maps of the planes
+ * (a depth view, a BVH heat view) are the host's: the reference defines none. */
+int wpt_first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits,
+                  float* normal3, float* albedo3, uint8_t* kind);
+/* Host-only (no session, no GPU): the primary rays gen_path makes, 6 f32 per pixel
+ * {origin = cam5[0..2], direction}; cam5 = {x, y, z, rot_x, rot_y}. */
+int wpt_primary_rays(uint32_t width, uint32_t height, const float* cam5, uint32_t frame_seed,
+                     uint32_t sample, float* rays6);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */
@@ -488,8 +511,11 @@ int wpt_debug_scene_info(void* h, uint64_t* out);
 int wpt_debug_scene_nodes4(void* h, uint32_t* out);
 /* 8 u32 per node: 6 f32 bounds bits (x_min,y_min,z_min,x_max,y_max,z_max), left_first, count */
 int wpt_debug_scene_nodes(void* h, uint32_t* out);
-/* 16 f32 per shape: geometry[12], kind, emissive, material rgb[...] packed as in wpt_scene.h */
+/* 16 f32 per shape: geometry[12] as in wpt_scene.h, kind, emissive, 0, 0 */
 int wpt_debug_scene_shapes(void* h, float* out);
+/* 4 f32 per shape: the Diffuse colour or the Emissive intensity (rgb), 1 if emissive
+ * (the rows of wpt_debug_scene_shapes stay geometry only) */
+int wpt_debug_scene_materials(void* h, float* out);
 int wpt_debug_scene_lights(void* h, uint32_t* out);
 /* The presolve's host restatement over the scene (as wpt_presolve_rays). */
 int wpt_debug_scene_presolve(void* h, size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out);

@@ -61,6 +61,8 @@ _SIGS = {
     "wpt_bvh_depth": (ctypes.c_int, []),
     "wpt_trace_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
     "wpt_shadow_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
+    "wpt_first_hit": (ctypes.c_int, [c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "wpt_primary_rays": (ctypes.c_int, [c_u32, c_u32, c_p, c_u32, c_u32, c_p]),
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),
@@ -85,6 +87,7 @@ _SIGS = {
     "wpt_adaptive_error": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_u32, c_p, c_p]),
     "wpt_adaptive_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_lights": (ctypes.c_int, [c_p, c_p]),
+    "wpt_debug_scene_materials": (ctypes.c_int, [c_p, c_p]),
     "wpt_debug_scene_free": (None, [c_p]),
     "wpt_debug_scene_new_gpu": (c_p, [c_i32, c_p, c_sz]),
     "wpt_debug_scene_build_info": (ctypes.c_int, [c_p, c_p]),

@@ -794,6 +794,34 @@ int wpt_trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out) {
   return WPT_OK;
 }
 
+int wpt_first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
+                  float* albedo3, uint8_t* kind) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  std::string err;
+  if (!g_session->renderer.first_hit(sample, dir3, t, id, visits, normal3, albedo3, kind, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+// gen_path's ray on the host: the same primary_dir (wpt_math.h) over the
+// constants Renderer::gen_params makes.
+int wpt_primary_rays(uint32_t width, uint32_t height, const float* cam5, uint32_t frame_seed, uint32_t sample,
+                     float* rays6) {
+  if (width == 0 || height == 0) return fail(WPT_ERR_INVALID_ARG, "empty viewport");
+  if (!cam5 || !rays6) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  const View v = make_view(width, height, cam5[3], cam5[4]);
+  for (uint32_t y = 0; y < height; y++)
+    for (uint32_t x = 0; x < width; x++) {
+      const uint32_t pixel = y * width + x;
+      uint32_t s = path_seed(frame_seed, pixel, sample);
+      const V3 d = primary_dir(x, y, s, v.w_inv, v.h_inv, v.ar, v.cx, v.sx, v.cy, v.sy);
+      float* r = rays6 + 6 * (size_t)pixel;
+      r[0] = cam5[0]; r[1] = cam5[1]; r[2] = cam5[2];
+      r[3] = d.x; r[4] = d.y; r[5] = d.z;
+    }
+  return WPT_OK;
+}
+
 int wpt_presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   if (n && (!rays || !resolved || !t_out || !id_out)) return fail(WPT_ERR_INVALID_ARG, "null argument");
@@ -935,6 +963,18 @@ int wpt_debug_scene_shapes(void* h, float* out) {
     o[13] = s.emissive ? 1.0f : 0.0f;
     o[14] = 0.0f;
     o[15] = 0.0f;
+  }
+  return WPT_OK;
+}
+
+int wpt_debug_scene_materials(void* h, float* out) {
+  const HostScene* sc = (const HostScene*)h;
+  if (!sc || !out) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  for (size_t i = 0; i < sc->shapes.size(); i++) {
+    const Shape& s = sc->shapes[i];
+    float* o = out + 4 * i;
+    memcpy(o, s.m, sizeof s.m);
+    o[3] = s.emissive ? 1.0f : 0.0f;
   }
   return WPT_OK;
 }

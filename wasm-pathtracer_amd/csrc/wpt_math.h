@@ -177,6 +177,32 @@ WPT_HD uint32_t path_seed(uint32_t frame_seed, uint32_t pixel, uint32_t sample) 
   h = fmix32(h ^ (sample * 0x27d4eb2fu + 0x165667b1u));
   return h == 0u ? 0x6d2b79f5u : h;
 }
+// The primary ray of pixel (x, y) (tracer.rs:178-191): two jitter draws from
+// the path's stream s, normalize, rot_x, rot_y. View: the frame's constants
+// (tracer.rs:167-172) and the camera's rotation. Called by the generate
+// kernels (gen_path) and by the host (wpt_primary_rays): the same bits.
+struct View {
+  float w_inv, h_inv, ar;
+  float cx, sx, cy, sy;  // cos/sin of rot_x, rot_y
+};
+WPT_HD View make_view(uint32_t w, uint32_t h, float rot_x, float rot_y) {
+  View v;
+  const float fw = (float)w, fh = (float)h;
+  v.w_inv = 1.0f / fw; v.h_inv = 1.0f / fh; v.ar = fw / fh;
+  v.cx = mcos(rot_x); v.sx = msin(rot_x);
+  v.cy = mcos(rot_y); v.sy = msin(rot_y);
+  return v;
+}
+WPT_HD V3 primary_dir(uint32_t x, uint32_t y, uint32_t& s, float w_inv, float h_inv, float ar, float cx, float sx,
+                      float cy, float sy) {
+  const float fx = (((float)x + xs_next(s)) * w_inv - 0.5f) * ar;
+  const float fy = 0.5f - ((float)y + xs_next(s)) * h_inv;
+  V3 v = normalize(mk(fx, fy, 0.8f));
+  v = mk(v.x, cx * v.y - sx * v.z, sx * v.y + cx * v.z);        // rot_x (vec3.rs:108-119)
+  v = mk(cy * v.x + sy * v.z, v.y, (-sy) * v.x + cy * v.z);     // rot_y (vec3.rs:95-106)
+  return v;
+}
+
 // Stream of photon k (PNEE preprocessing, tracer.rs:126-152): a separate
 // domain of the same hash (build-defined, like path_seed).
 WPT_HD uint32_t photon_seed(uint32_t frame_seed, uint32_t k) {

@@ -317,6 +317,10 @@ class Renderer {
   uint32_t tile() const { return tile_; }
   bool unpack_ranks(const float4* gathered, uint64_t slot, std::string& err);
   bool trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err);
+  // first-hit feature planes of sample `sample` of every frame pixel
+  // (wpt_first_hit, include/wpt.h); a null plane is not computed
+  bool first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
+                 float* albedo3, uint8_t* kind, std::string& err);
   // test hook: presolve_ray on the device over caller-given rays
   bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
   // test hook: presolve_shadow on the device over caller-given {p, q} pairs
@@ -388,6 +392,7 @@ class Renderer {
   // the Batch state machine: lanes and generate; bounces until done or a
   // live-count read is pending (block: wait for it); the tail
   auto shade_params() const;  // the ShadeParams of a batch's shade kernels (wpt_render.hip)
+  auto gen_params(uint32_t npix) const;  // the GenParams of a mapping over npix entries (wpt_render.hip)
   bool batch_begin(Batch& B, std::string& err);
   bool batch_advance(Batch& B, bool block, std::string& err);
   bool batch_tail(Batch& B, std::string& err);
@@ -659,6 +664,12 @@ class Renderer {
   std::vector<uint32_t> probe_meta_;
   uint4* probe_slot(const LaunchCtx& C, int kernel, uint32_t grid);
   uint32_t* d_fallback_ = nullptr; // [2] rays re-traced exactly (extend, shadow)
+  // first_hit's own buffers, kept between calls: the overflow flag and the
+  // planes; the traversal-stack spill area of its grid
+  void* d_fh_ = nullptr;
+  size_t fh_cap_ = 0;
+  uint2* d_fh_spill_ = nullptr;
+  size_t fh_spill_cap_ = 0;
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];
   int lanes_made_ = 0;

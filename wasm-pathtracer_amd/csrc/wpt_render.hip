@@ -691,7 +691,11 @@ __device__ __forceinline__ void expand_pair(const DevScene& S, const Hot& H, con
 // k_trace, round 4.)
 // SHADOW: `occluded` is set on the early exit (a non-light shape hit strictly
 // before `early` proves the reference's closest hit is an occluder).
-template <bool SHADOW, bool TRI_ONLY, bool COUNT, bool LB = true>
+// REF_VISITS (with COUNT; wpt_first_hit.h): `visits` counts as the reference's
+// num_bvh_hits does, one more for an expanded node whose left box test fails:
+// its right child then goes through traverse_bvh_guarded, which counts itself
+// (scene.rs:284).
+template <bool SHADOW, bool TRI_ONLY, bool COUNT, bool LB = true, bool REF_VISITS = false>
 __device__ __forceinline__ bool step(const DevScene& S, const Hot& H, Lane& L, const Stack& stk, int32_t light,
                                      float early, bool& occluded, uint32_t& visits, uint32_t& tests,
                                      uint32_t& nbytes) {
@@ -707,6 +711,7 @@ __device__ __forceinline__ bool step(const DevScene& S, const Hot& H, Lane& L, c
     uint32_t c[4];
     const uint32_t lf0 = L.lf;
     expand_pair(S, H, L, L.best, hl, hr, ld, rd, c);
+    if (COUNT && REF_VISITS && !hl) visits++;
     do_pop = !hl && !hr;
     if (!do_pop) {
       const bool left_first = hl && (!hr || ld < rd);  // ties: right first (scene.rs:244)
@@ -901,13 +906,8 @@ __device__ __forceinline__ GenPath gen_path(const GenParams& P, const uint32_t* 
   g.pixel = part_pix ? part_pix[g.row] : g.row;
   const uint32_t x = g.pixel % P.W, y = g.pixel / P.W;
   uint32_t s = path_seed(P.seed, g.pixel, g.sample);
-  const float fx = (((float)x + xs_next(s)) * P.w_inv - 0.5f) * P.ar;
-  const float fy = 0.5f - ((float)y + xs_next(s)) * P.h_inv;
-  V3 v = normalize(mk(fx, fy, 0.8f));
-  v = mk(v.x, P.cx * v.y - P.sx * v.z, P.sx * v.y + P.cx * v.z);        // rot_x (vec3.rs:108-119)
-  v = mk(P.cy * v.x + P.sy * v.z, v.y, (-P.sy) * v.x + P.cy * v.z);     // rot_y (vec3.rs:95-106)
+  g.v = primary_dir(x, y, s, P.w_inv, P.h_inv, P.ar, P.cx, P.sx, P.cy, P.sy);
   g.s = s;
-  g.v = v;
   g.type = x < P.half ? P.left_type : P.right_type;
   return g;
 }
@@ -2548,6 +2548,8 @@ __global__ void k_pack_partition(const uint32_t* __restrict__ part_pix, uint32_t
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
+#include "wpt_first_hit.h"
+
 }  // namespace
 
 // ===========================================================================
@@ -2673,6 +2675,8 @@ Renderer::~Renderer() {
   if (d_work_) (void)hipFree(d_work_);
   if (d_probe_) (void)hipFree(d_probe_);
   if (d_fallback_) (void)hipFree(d_fallback_);
+  if (d_fh_) (void)hipFree(d_fh_);
+  if (d_fh_spill_) (void)hipFree(d_fh_spill_);
   for (PathSet& L : lanes_) {
     if (L.counts) (void)hipFree(L.counts);
     if (L.h_counts) (void)hipHostFree(L.h_counts);
@@ -3012,7 +3016,8 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 28:
     case 29:
     case 41:
-    case 43: err = "read-only option"; return false;
+    case 43:
+    case 44: err = "read-only option"; return false;
     case 24:
       if (!range(1, kMaxLanes - kAsyncLane0 - 1)) return false;  // the fill lane follows them
       if (!drain_async(err)) return false;
@@ -3074,6 +3079,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 24: v = stock_lanes_; return true;
     case 42: v = stock_ranks_ ? 1 : 0; return true;
     case 43: v = (int64_t)ring_bytes(); return true;
+    case 44: v = (int64_t)w_ | ((int64_t)h_ << 32); return true;  // read-only: the viewport
     default: return false;
   }
 }
@@ -3378,6 +3384,22 @@ auto Renderer::shade_params() const {
   return ShadeParams{max_depth_, debug_, drop_miss_ ? 1 : 0, presolve_shadow_ && light_guards_ != 0 ? 1 : 0};
 }
 
+// The frame, camera, seed and render types as the generate kernels take them,
+// for a mapping over npix entries.
+auto Renderer::gen_params(uint32_t npix) const {
+  GenParams G;
+  G.W = w_; G.H = h_; G.npix = npix;
+  const View v = make_view(w_, h_, cam_[3], cam_[4]);
+  G.w_inv = v.w_inv; G.h_inv = v.h_inv; G.ar = v.ar;
+  G.cam[0] = cam_[0]; G.cam[1] = cam_[1]; G.cam[2] = cam_[2];
+  G.cx = v.cx; G.sx = v.sx;
+  G.cy = v.cy; G.sy = v.sy;
+  G.seed = seed_;
+  G.half = w_ / 2;
+  G.left_type = (uint32_t)left_type_; G.right_type = (uint32_t)right_type_;
+  return G;
+}
+
 // Lanes, slices and bounce 0 of batch B (k_generate on each lane's stream,
 // after the main stream's work so far: reset, round planning, k_spec_plan).
 bool Renderer::batch_begin(Batch& B, std::string& err) {
@@ -3389,16 +3411,7 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   const uint32_t* rnd_base = B.moff ? B.mbase : round ? rounds_[B.half].rbase : nullptr;
   const uint32_t npix = B.moff ? B.nent : B.part ? B.npix : (uint32_t)part_pix_.size();
   const uint32_t* part = B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
-  GenParams G;
-  G.W = w_; G.H = h_; G.npix = npix;
-  const float fw = (float)w_, fh = (float)h_;
-  G.w_inv = 1.0f / fw; G.h_inv = 1.0f / fh; G.ar = fw / fh;  // tracer.rs:167-172
-  G.cam[0] = cam_[0]; G.cam[1] = cam_[1]; G.cam[2] = cam_[2];
-  G.cx = mcos(cam_[3]); G.sx = msin(cam_[3]);
-  G.cy = mcos(cam_[4]); G.sy = msin(cam_[4]);
-  G.seed = seed_;
-  G.half = w_ / 2;
-  G.left_type = (uint32_t)left_type_; G.right_type = (uint32_t)right_type_;
+  const GenParams G = gen_params(npix);
   const uint32_t slots = B.stock ? stock_used_slots_ : 0u;
   for (int i = 0; i <= B.nl; i++) B.off[i] = B.n * (uint64_t)i / (uint64_t)B.nl;
   // RR-only batches (the k_finish hand-over reads one live count per lane)
@@ -5344,6 +5357,76 @@ bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id
   HIP_OK(hipMemcpyAsync(t_out, L.t, 4 * n, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipMemcpyAsync(id_out, L.id, 4 * n, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
+  return true;
+}
+
+// First-hit feature planes of the whole frame (wpt_first_hit.h), on the main
+// stream after its work so far, in buffers of its own (kept for the next call;
+// its own overflow flag too): the session's frame, rounds, stock, counters and
+// timings are neither read nor written.
+bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
+                         float* albedo3, uint8_t* kind, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
+  const uint32_t mask = (dir3 ? kFhDir : 0u) | (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) |
+                        (normal3 ? kFhNormal : 0u) | (albedo3 ? kFhAlbedo : 0u) | (kind ? kFhKind : 0u);
+  if (mask == 0) return true;
+  const size_t np = (size_t)w_ * h_;
+  // the flag, then the planes wanted, each 256 B aligned
+  void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
+  const size_t elem[7] = {12, 4, 4, 4, 12, 12, 1};
+  size_t off[7], need = 256;
+  for (int k = 0; k < 7; k++) {
+    off[k] = need;
+    if (host[k]) need += (elem[k] * np + 255) / 256 * 256;
+  }
+  if (need > fh_cap_) {
+    if (d_fh_) (void)hipFree(d_fh_);
+    d_fh_ = nullptr;
+    fh_cap_ = 0;
+    HIP_OK(hipMalloc(&d_fh_, need));
+    fh_cap_ = need;
+  }
+  FirstHitParams P;
+  P.G = gen_params((uint32_t)np);
+  P.sample = sample;
+  P.mask = mask;
+  P.tiles_x = (w_ + kFhTile - 1) / kFhTile;
+  P.ntiles = P.tiles_x * ((h_ + kFhTile - 1) / kFhTile);
+  char* base = (char*)d_fh_;
+  P.dir = (float*)(base + off[0]);
+  P.t = (float*)(base + off[1]);
+  P.id = (int32_t*)(base + off[2]);
+  P.visits = (uint32_t*)(base + off[3]);
+  P.normal = (float*)(base + off[4]);
+  P.albedo = (float*)(base + off[5]);
+  P.kind = (uint8_t*)(base + off[6]);
+  // one block per kTBlock / 64 tiles, clamped to a spill area of kFhSpillBytes
+  // (deep trees: the blocks then take further tiles a grid stride on)
+  constexpr size_t kFhSpillBytes = 256ull << 20;
+  const size_t per_block = spill_slots() * kTBlock * sizeof(uint2);
+  const uint32_t want = (P.ntiles + kTBlock / 64 - 1) / (kTBlock / 64);
+  const uint32_t g = (uint32_t)std::max<size_t>(1, std::min<size_t>(want, kFhSpillBytes / per_block));
+  if ((size_t)g * per_block > fh_spill_cap_) {
+    if (d_fh_spill_) (void)hipFree(d_fh_spill_);
+    d_fh_spill_ = nullptr;
+    fh_spill_cap_ = 0;
+    HIP_OK(hipMalloc(&d_fh_spill_, (size_t)g * per_block));
+    fh_spill_cap_ = (size_t)g * per_block;
+  }
+  DevScene ds = ds_;
+  ds.probe = nullptr;
+  ds.overflow = (uint32_t*)d_fh_;
+  HIP_OK(hipMemsetAsync(d_fh_, 0, sizeof(uint32_t), stream_));
+  if (ds_.tri_only) k_first_hit<true><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
+  else k_first_hit<false><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
+  HIP_OK(hipGetLastError());
+  uint32_t flag = 0;
+  HIP_OK(hipMemcpyAsync(&flag, d_fh_, sizeof flag, hipMemcpyDeviceToHost, stream_));
+  for (int k = 0; k < 7; k++)
+    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], base + off[k], elem[k] * np, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (flag) { err = "traversal stack overflow (results invalid)"; return false; }
   return true;
 }
 

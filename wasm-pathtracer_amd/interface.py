@@ -357,7 +357,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
            "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41,
-           "stock_ranks": 42, "stock_ring_bytes": 43}
+           "stock_ranks": 42, "stock_ring_bytes": 43, "viewport": 44}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -429,6 +429,38 @@ def shadow_rays(pq, light_ids):
     return occ.astype(bool)
 
 
+FIRST_HIT_PLANES = {  # name -> (argument position in wpt_first_hit, dtype, components)
+    "dir": (0, np.float32, 3), "t": (1, np.float32, 1), "id": (2, np.int32, 1), "visits": (3, np.uint32, 1),
+    "normal": (4, np.float32, 3), "albedo": (5, np.float32, 3), "kind": (6, np.uint8, 1),
+}
+
+
+def first_hit(sample=0, planes=("dir", "t", "id", "visits", "normal", "albedo", "kind")):
+    """First-hit feature planes of sample `sample` of every frame pixel
+    (wpt_first_hit): a dict plane name -> (H, W) or (H, W, 3) array of the
+    planes asked for. t is +inf and id -1 on a miss; kind is 0 miss, 1 diffuse,
+    2 emissive."""
+    vp = get_option("viewport")
+    w, h = vp & 0xFFFFFFFF, vp >> 32
+    out, ptr = {}, [None] * 7
+    for name in planes:
+        pos, dt, c = FIRST_HIT_PLANES[name]
+        out[name] = np.empty((h, w, 3) if c == 3 else (h, w), dtype=dt)
+        ptr[pos] = out[name].ctypes.data
+    _check(lib().wpt_first_hit(sample, *ptr))
+    return out
+
+
+def primary_rays(width, height, cam, seed=0xBABABEBE, sample=0):
+    """The primary rays of a width x height frame as the generate kernels make
+    them (wpt_primary_rays; host only, no session): (height * width, 6) f32
+    {origin, direction} in raster order. cam = (x, y, z, rot_x, rot_y)."""
+    c = np.ascontiguousarray(cam, dtype=np.float32).reshape(5)
+    rays = np.empty((width * height, 6), dtype=np.float32)
+    _check(lib().wpt_primary_rays(width, height, c.ctypes.data, seed, sample, rays.ctypes.data))
+    return rays
+
+
 def presolve_rays(rays):
     """The producers' presolve on the device (wpt_presolve_rays): per ray
     (resolved, t, id); (t, id) is the closest hit of a resolved ray."""
@@ -490,6 +522,12 @@ class DebugScene:
     def shapes(self):
         out = np.empty((self.num_shapes, 16), dtype=np.float32)
         lib().wpt_debug_scene_shapes(self.h, out.ctypes.data)
+        return out
+
+    def materials(self):
+        """(shapes, 4) f32: Diffuse colour or Emissive intensity, 1 if emissive."""
+        out = np.empty((self.num_shapes, 4), dtype=np.float32)
+        _check(lib().wpt_debug_scene_materials(self.h, out.ctypes.data))
         return out
 
     def lights(self):
