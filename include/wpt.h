@@ -425,6 +425,9 @@ int wpt_set_lanes(int32_t n);
                                        using its ring (WPT_OPT_STOCK 0, WPT_OPT_STOCK_RANKS 0, another partition or viewport)
                                        keeps the blocks, and this value, until it sizes its next ring or ends */
 #define WPT_OPT_VIEWPORT 44      /* read-only: the session's viewport, width | height << 32 (the size of wpt_first_hit's planes) */
+#define WPT_OPT_DENOISE_LDS 45   /* bit i: iteration i of wpt_denoise (step 1 << i, i = 0..2) runs the kernel that stages its tile
+                                    and halo in LDS; clear: the kernel that reads its taps from global memory, as steps 8 and
+                                    16 always do. The same bits either way (default 7) */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -485,6 +488,40 @@ int wpt_first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t*
  * {origin = cam5[0..2], direction}; cam5 = {x, y, z, rot_x, rot_y}. */
 int wpt_primary_rays(uint32_t width, uint32_t height, const float* cam5, uint32_t frame_seed,
                      uint32_t sample, float* rays6);
+/* Edge-avoiding a-trous filter (Dammertz et al. 2010) of the session's frame as
+ * the calling rank holds it, guided by the first-hit planes of sample `sample`
+ * (depth, normal, albedo, kind: wpt_first_hit's, made on the device, no host
+ * round trip). The stencil is the reference's GAUSS5 (render_target.rs:21-27)
+ * at steps 1, 2, 4, ... for `iterations` (1..5) passes; the colour weight
+ * 1 / (1 + |dc|^2 / sig^2) starts at sig = sigma_c and halves per pass, the
+ * normal weight is max(n_p . n_q, 0)^32, the depth weight 1 / (1 + r^2) with
+ * r = |t_p - t_q| / (sigma_z * t_p * step); taps of another kind (miss /
+ * diffuse / emissive) or without a finite mean are never read. flags:
+ * WPT_DENOISE_ALBEDO filters radiance / albedo on diffuse hits and multiplies
+ * the albedo back. The definition to the operation: DESIGN.md §2; every output
+ * bit is that of wpt_denoise_host on the same planes while |acc / cnt| <= 2^100.
+ *  rgb3   3 f32  the filtered mean; +0 where valid is 0
+ *  valid  u8     1 where the pixel has samples and a finite mean (on a partitioned
+ *                session the other ranks' pixels have none until wpt_gather_frame)
+ *  rgba   4 u8   (clamp(rgb, 0, 1) * 255) as u8, alpha 255 (render_target.rs:62-64)
+ * Any output may be NULL; with all of them NULL nothing is launched. The session
+ * (accumulation, rounds, sample stock, wpt_stats, wpt_kernel_times) is not touched.
+ * WPT_ERR_INVALID_ARG: iterations 0 or above 5, a sigma not finite or <= 0, an
+ * unknown flag; for the two functions below also a null input, W*H == 0 or >= 2^32. */
+#define WPT_DENOISE_ALBEDO 1u
+int wpt_denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
+                uint8_t* valid, uint8_t* rgba);
+/* Test hook: the same kernels and launch geometry on a caller's W x H planes
+ * (acc3, cnt as wpt_read_radiance gives them; t, normal3, albedo3, kind as
+ * wpt_first_hit does), in buffers of its own. Needs wpt_init. */
+int wpt_denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                       const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                       float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba);
+/* Host only (no session, no GPU): the filter's restatement, the same functions
+ * the kernels call. */
+int wpt_denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                     const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                     float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */

@@ -24,6 +24,10 @@ def functions(path):
 
 def norm(body):
     body = re.sub(r"\.LBB\d+_", ".LBB_", body)
+    # the loop comments name blocks too, and their column follows the label's
+    # length (a function number going from two digits to three)
+    body = re.sub(r"\bBB\d+_", "BB_", body)
+    body = re.sub(r"[ \t]+;", " ;", body)
     body = re.sub(r"\.Lfunc_(begin|end)\d+", ".Lfunc_", body)
     return re.sub(r"\.Ltmp\d+", ".Ltmp", body)
 

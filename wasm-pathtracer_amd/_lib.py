@@ -63,6 +63,11 @@ _SIGS = {
     "wpt_shadow_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p]),
     "wpt_first_hit": (ctypes.c_int, [c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "wpt_primary_rays": (ctypes.c_int, [c_u32, c_u32, c_p, c_u32, c_u32, c_p]),
+    "wpt_denoise": (ctypes.c_int, [c_u32, c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
+    "wpt_denoise_planes": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_u32, c_f32, c_f32, c_u32,
+                                          c_p, c_p, c_p]),
+    "wpt_denoise_host": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_u32, c_f32, c_f32, c_u32,
+                                        c_p, c_p, c_p]),
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),

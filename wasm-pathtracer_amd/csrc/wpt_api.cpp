@@ -23,6 +23,8 @@ using namespace wpt;
 
 namespace {
 
+#include "wpt_denoise.h"  // the host part: the restatement wpt_denoise_host runs
+
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
   std::map<uint32_t, std::vector<float>> meshes;    // Mesh::Triangled, as raw vertex triples
@@ -819,6 +821,55 @@ int wpt_primary_rays(uint32_t width, uint32_t height, const float* cam5, uint32_
       r[0] = cam5[0]; r[1] = cam5[1]; r[2] = cam5[2];
       r[3] = d.x; r[4] = d.y; r[5] = d.z;
     }
+  return WPT_OK;
+}
+
+namespace {
+// the argument rules wpt_denoise, wpt_denoise_planes and wpt_denoise_host share
+const char* denoise_args(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags) {
+  if (iterations == 0 || iterations > kDnMaxIter) return "denoise: iterations 1..5";
+  if (!dn_finite(sigma_c) || !(sigma_c > 0.0f) || !dn_finite(sigma_z) || !(sigma_z > 0.0f))
+    return "denoise: sigmas must be finite and > 0";
+  if (flags & ~(uint32_t)WPT_DENOISE_ALBEDO) return "denoise: unknown flag";
+  return nullptr;
+}
+const char* denoise_plane_args(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                               const float* normal3, const float* albedo3, const uint8_t* kind) {
+  if (!acc3 || !cnt || !t || !normal3 || !albedo3 || !kind) return "null pointer";
+  if ((uint64_t)W * H == 0 || (uint64_t)W * H >= (1ull << 32)) return "bad frame size";
+  return nullptr;
+}
+}  // namespace
+
+int wpt_denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
+                uint8_t* valid, uint8_t* rgba) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.denoise(sample, iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                       const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                       float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = denoise_plane_args(W, H, acc3, cnt, t, normal3, albedo3, kind)) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.denoise_planes(W, H, acc3, cnt, t, normal3, albedo3, kind, iterations, sigma_c, sigma_z,
+                                          flags, rgb3, valid, rgba, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                     const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                     float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = denoise_plane_args(W, H, acc3, cnt, t, normal3, albedo3, kind)) return fail(WPT_ERR_INVALID_ARG, e);
+  denoise_host(W, H, acc3, cnt, t, normal3, albedo3, kind, iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba);
   return WPT_OK;
 }
 

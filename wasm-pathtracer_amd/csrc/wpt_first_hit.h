@@ -32,6 +32,7 @@
 
 constexpr uint32_t kFhDir = 1u, kFhT = 2u, kFhId = 4u, kFhVisits = 8u, kFhNormal = 16u, kFhAlbedo = 32u,
                    kFhKind = 64u;
+constexpr size_t kFhElem[7] = {12, 4, 4, 4, 12, 12, 1};  // bytes per pixel of the planes, in kFh* bit order
 constexpr uint32_t kFhTile = 8;  // pixels per tile side: kFhTile^2 = one wave
 static_assert(kFhTile * kFhTile == 64 && kTBlock % 64 == 0, "a wave per tile");
 

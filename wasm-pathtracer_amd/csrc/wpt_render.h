@@ -321,6 +321,15 @@ class Renderer {
   // (wpt_first_hit, include/wpt.h); a null plane is not computed
   bool first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
                  float* albedo3, uint8_t* kind, std::string& err);
+  // the a-trous filter (wpt_denoise.h) on the session's frame, guided by the
+  // first-hit planes of `sample` (wpt_denoise); a null output is not written
+  bool denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
+               uint8_t* valid, uint8_t* rgba, std::string& err);
+  // test hook: the same kernels and launch geometry on a caller's planes
+  bool denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                      const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                      float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba,
+                      std::string& err);
   // test hook: presolve_ray on the device over caller-given rays
   bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
   // test hook: presolve_shadow on the device over caller-given {p, q} pairs
@@ -670,6 +679,18 @@ class Renderer {
   size_t fh_cap_ = 0;
   uint2* d_fh_spill_ = nullptr;
   size_t fh_spill_cap_ = 0;
+  // k_first_hit of the planes in `mask` into d_fh_ (plane k at off[k]); waits for it
+  bool first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err);
+  // denoise's scratch for the session's viewport (records A0, A1, B, a' and
+  // the outputs), made on first use, freed with the viewport; the filter
+  // itself over device planes in a scratch of dn_bytes(W * H)
+  void* d_dn_ = nullptr;
+  size_t dn_cap_ = 0;
+  static size_t dn_bytes(size_t np);
+  bool dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
+              const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
+              float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
+  uint32_t dn_lds_ = 7;  // WPT_OPT_DENOISE_LDS
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];
   int lanes_made_ = 0;

@@ -2549,6 +2549,8 @@ __global__ void k_pack_partition(const uint32_t* __restrict__ part_pix, uint32_t
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 #include "wpt_first_hit.h"
+#define WPT_DENOISE_KERNELS
+#include "wpt_denoise.h"
 
 }  // namespace
 
@@ -2677,6 +2679,7 @@ Renderer::~Renderer() {
   if (d_fallback_) (void)hipFree(d_fallback_);
   if (d_fh_) (void)hipFree(d_fh_);
   if (d_fh_spill_) (void)hipFree(d_fh_spill_);
+  if (d_dn_) (void)hipFree(d_dn_);
   for (PathSet& L : lanes_) {
     if (L.counts) (void)hipFree(L.counts);
     if (L.h_counts) (void)hipHostFree(L.h_counts);
@@ -3007,6 +3010,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 38: if (!range(0, 1)) return false; drop_miss_ = v != 0; return true;
     case 39: if (!range(0, 1)) return false; presolve_shadow_ = v != 0; return true;
     case 40: if (!range(0, 1)) return false; gen_shade_ = v != 0; return true;
+    case 45: if (!range(0, 7)) return false; dn_lds_ = (uint32_t)v; return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -3065,6 +3069,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 38: v = drop_miss_ ? 1 : 0; return true;
     case 39: v = presolve_shadow_ ? 1 : 0; return true;
     case 40: v = gen_shade_ ? 1 : 0; return true;
+    case 45: v = dn_lds_; return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -3097,7 +3102,9 @@ bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
   if (d_cnt_) (void)hipFree(d_cnt_);
   if (d_rgba_) (void)hipFree(d_rgba_);
   if (d_samp_) (void)hipFree(d_samp_);
+  if (d_dn_) (void)hipFree(d_dn_);
   d_acc_ = nullptr; d_cnt_ = nullptr; d_rgba_ = nullptr; d_samp_ = nullptr;
+  d_dn_ = nullptr; dn_cap_ = 0;
   HIP_OK(hipMalloc(&d_acc_, sizeof(float4) * (size_t)w * h));
   HIP_OK(hipMalloc(&d_cnt_, sizeof(uint32_t) * (size_t)w * h));
   HIP_OK(hipMalloc(&d_rgba_, 4 * (size_t)w * h));
@@ -5366,19 +5373,33 @@ bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id
 // timings are neither read nor written.
 bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
                          float* albedo3, uint8_t* kind, std::string& err) {
-  if (!scene_ok_) { err = "no scene"; return false; }
-  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   const uint32_t mask = (dir3 ? kFhDir : 0u) | (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) |
                         (normal3 ? kFhNormal : 0u) | (albedo3 ? kFhAlbedo : 0u) | (kind ? kFhKind : 0u);
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   if (mask == 0) return true;
+  size_t off[7];
+  if (!first_hit_launch(sample, mask, off, err)) return false;
+  const size_t np = (size_t)w_ * h_;
+  void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
+  for (int k = 0; k < 7; k++)
+    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], (char*)d_fh_ + off[k], kFhElem[k] * np, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return true;
+}
+
+// k_first_hit of the planes in `mask` (bit k = plane k of wpt_first_hit's
+// order) into d_fh_, plane k at byte off[k]; returns once the kernel has ended
+// without a stack overflow.
+bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   const size_t np = (size_t)w_ * h_;
   // the flag, then the planes wanted, each 256 B aligned
-  void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
-  const size_t elem[7] = {12, 4, 4, 4, 12, 12, 1};
-  size_t off[7], need = 256;
+  size_t need = 256;
   for (int k = 0; k < 7; k++) {
     off[k] = need;
-    if (host[k]) need += (elem[k] * np + 255) / 256 * 256;
+    if (mask >> k & 1u) need += (kFhElem[k] * np + 255) / 256 * 256;
   }
   if (need > fh_cap_) {
     if (d_fh_) (void)hipFree(d_fh_);
@@ -5423,11 +5444,144 @@ bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, ui
   HIP_OK(hipGetLastError());
   uint32_t flag = 0;
   HIP_OK(hipMemcpyAsync(&flag, d_fh_, sizeof flag, hipMemcpyDeviceToHost, stream_));
-  for (int k = 0; k < 7; k++)
-    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], base + off[k], elem[k] * np, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   if (flag) { err = "traversal stack overflow (results invalid)"; return false; }
   return true;
+}
+
+// ---------------------------------------------------------------------------
+// The a-trous filter (wpt_denoise.h)
+// ---------------------------------------------------------------------------
+
+// Scratch of a frame of np pixels: the records A0, A1 and B, a', then the
+// outputs rgb, rgba and valid; every part 256 B aligned.
+namespace {
+struct DnLayout {
+  size_t a0, a1, b, ap, rgb, rgba, valid, bytes;
+  explicit DnLayout(size_t np) {
+    size_t at = 0;
+    auto take = [&](size_t elem) {
+      const size_t o = at;
+      at += (elem * np + 255) / 256 * 256;
+      return o;
+    };
+    a0 = take(16); a1 = take(16); b = take(16); ap = take(12); rgb = take(12); rgba = take(4); valid = take(1);
+    bytes = at;
+  }
+};
+
+template <int STEP>
+void launch_atrous(bool lds, dim3 grid, hipStream_t s, const float4* A, const float4* B, uint32_t W, uint32_t H,
+                   float s2, float sigma_z, float4* Aout) {
+  if constexpr (STEP <= 4) {
+    if (lds) {
+      k_dn_atrous<STEP, true><<<grid, kBlock, 0, s>>>(A, B, W, H, s2, sigma_z, Aout);
+      return;
+    }
+  }
+  k_dn_atrous<STEP, false><<<grid, kBlock, 0, s>>>(A, B, W, H, s2, sigma_z, Aout);
+}
+}  // namespace
+
+size_t Renderer::dn_bytes(size_t np) { return DnLayout(np).bytes; }
+
+// Pack, the iterations and unpack over device planes, on lane 0's stream,
+// neither timed nor counted; the outputs wanted are copied to the host and
+// waited for. Iteration i runs the LDS kernel if bit i of WPT_OPT_DENOISE_LDS
+// is set (steps 1, 2, 4 only), else the direct one.
+bool Renderer::dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
+                      const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
+                      uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                      uint8_t* rgba, std::string& err) {
+  const LaunchCtx C = lane0_ctx(false);
+  hipStream_t s = C.stream;
+  const size_t np = (size_t)W * H;
+  const DnLayout Z(np);
+  float4* A[2] = {(float4*)(scratch + Z.a0), (float4*)(scratch + Z.a1)};
+  float4* B = (float4*)(scratch + Z.b);
+  float* ap = (float*)(scratch + Z.ap);
+  float* d_rgb = rgb3 ? (float*)(scratch + Z.rgb) : nullptr;
+  uint8_t* d_rgba = rgba ? (uint8_t*)(scratch + Z.rgba) : nullptr;
+  uint8_t* d_valid = valid ? (uint8_t*)(scratch + Z.valid) : nullptr;
+  k_dn_pack<<<blocks_for(np), kBlock, 0, s>>>(acc, cnt, t, normal, albedo, kind, (uint32_t)np, flags, A[0], B, ap);
+  HIP_OK(hipGetLastError());
+  const dim3 grid((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile);
+  float sig = sigma_c;
+  int cur = 0;
+  for (uint32_t i = 0; i < iterations; i++) {
+    const float s2 = sig * sig;
+    const bool lds = (dn_lds_ >> i & 1u) != 0;
+    switch (i) {
+      case 0: launch_atrous<1>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
+      case 1: launch_atrous<2>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
+      case 2: launch_atrous<4>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
+      case 3: launch_atrous<8>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
+      default: launch_atrous<16>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
+    }
+    HIP_OK(hipGetLastError());
+    cur ^= 1;
+    sig = sig * 0.5f;
+  }
+  k_dn_unpack<<<blocks_for(np), kBlock, 0, s>>>(A[cur], B, ap, (uint32_t)np, d_rgb, d_valid, d_rgba);
+  HIP_OK(hipGetLastError());
+  if (rgb3) HIP_OK(hipMemcpyAsync(rgb3, d_rgb, 12 * np, hipMemcpyDeviceToHost, s));
+  if (valid) HIP_OK(hipMemcpyAsync(valid, d_valid, np, hipMemcpyDeviceToHost, s));
+  if (rgba) HIP_OK(hipMemcpyAsync(rgba, d_rgba, 4 * np, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return true;
+}
+
+// The session's frame as this rank holds it, guided by k_first_hit's planes
+// of `sample`, which stay on the device. The frame, the counts, the rounds,
+// the stock and the counters are only read.
+bool Renderer::denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                       float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
+  if (!rgb3 && !valid && !rgba) return true;
+  size_t off[7];
+  if (!first_hit_launch(sample, kFhT | kFhNormal | kFhAlbedo | kFhKind, off, err)) return false;
+  const size_t need = dn_bytes((size_t)w_ * h_);
+  if (need > dn_cap_) {
+    if (d_dn_) (void)hipFree(d_dn_);
+    d_dn_ = nullptr;
+    dn_cap_ = 0;
+    HIP_OK(hipMalloc(&d_dn_, need));
+    dn_cap_ = need;
+  }
+  const char* fh = (const char*)d_fh_;
+  return dn_run(w_, h_, d_acc_, d_cnt_, (const float*)(fh + off[1]), (const float*)(fh + off[4]),
+                (const float*)(fh + off[5]), (const uint8_t*)(fh + off[6]), (char*)d_dn_, iterations, sigma_c, sigma_z,
+                flags, rgb3, valid, rgba, err);
+}
+
+bool Renderer::denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                              const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                              float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                              uint8_t* rgba, std::string& err) {
+  if (!stream_) { err = "no device"; return false; }
+  if (!rgb3 && !valid && !rgba) return true;
+  const size_t np = (size_t)W * H;
+  HookScratch S;
+  float4* d_acc = S.d<float4>(np);
+  uint32_t* d_cnt = S.d<uint32_t>(np);
+  float* d_t = S.d<float>(np);
+  float* d_n = S.d<float>(3 * np);
+  float* d_al = S.d<float>(3 * np);
+  uint8_t* d_kind = S.d<uint8_t>(np);
+  char* scratch = S.d<char>(dn_bytes(np));
+  if (!S.ok) { err = "hipMalloc failed (denoise_planes)"; return false; }
+  std::vector<float4> a4(np);
+  for (size_t i = 0; i < np; i++) a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
+  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_t, t, sizeof(float) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_al, albedo3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return dn_run(W, H, d_acc, d_cnt, d_t, d_n, d_al, d_kind, scratch, iterations, sigma_c, sigma_z, flags, rgb3, valid,
+                rgba, err);
 }
 
 bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out,

@@ -357,7 +357,8 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "stock_ahead": 30, "async_oneshot": 31, "stock_every": 32, "stock_extra": 33,
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
            "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41,
-           "stock_ranks": 42, "stock_ring_bytes": 43, "viewport": 44}
+           "stock_ranks": 42, "stock_ring_bytes": 43, "viewport": 44,
+           "denoise_lds": 45}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -459,6 +460,64 @@ def primary_rays(width, height, cam, seed=0xBABABEBE, sample=0):
     rays = np.empty((width * height, 6), dtype=np.float32)
     _check(lib().wpt_primary_rays(width, height, c.ctypes.data, seed, sample, rays.ctypes.data))
     return rays
+
+
+DENOISE_ALBEDO = 1  # WPT_DENOISE_ALBEDO: filter radiance / albedo on diffuse hits, multiply the albedo back
+# the documented defaults of denoise(): see profiles/denoise/README.md
+DENOISE_DEFAULTS = {"iterations": 3, "sigma_c": 1.0, "sigma_z": 0.1, "flags": DENOISE_ALBEDO}
+
+
+def _denoise_out(w, h):
+    rgb = np.empty((h, w, 3), dtype=np.float32)
+    valid = np.empty((h, w), dtype=np.uint8)
+    rgba = np.empty((h, w, 4), dtype=np.uint8)
+    return rgb, valid, rgba
+
+
+def denoise(sample=0, iterations=DENOISE_DEFAULTS["iterations"], sigma_c=DENOISE_DEFAULTS["sigma_c"],
+            sigma_z=DENOISE_DEFAULTS["sigma_z"], flags=DENOISE_DEFAULTS["flags"]):
+    """The session's frame through the edge-avoiding a-trous filter
+    (wpt_denoise), guided by the first-hit planes of sample `sample`:
+    (rgb (H, W, 3) f32, valid (H, W) u8, rgba (H, W, 4) u8). Defaults: 3
+    iterations (steps 1, 2, 4), sigma_c 1.0 (halved per iteration), sigma_z 0.1,
+    albedo demodulation on. The session is not touched."""
+    vp = get_option("viewport")
+    rgb, valid, rgba = _denoise_out(vp & 0xFFFFFFFF, vp >> 32)
+    _check(lib().wpt_denoise(sample, iterations, sigma_c, sigma_z, flags, rgb.ctypes.data, valid.ctypes.data,
+                             rgba.ctypes.data))
+    return rgb, valid, rgba
+
+
+def _denoise_planes(fn, acc, cnt, t, normal, albedo, kind, iterations, sigma_c, sigma_z, flags):
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    h, w = cnt.shape
+    acc = np.ascontiguousarray(acc, dtype=np.float32).reshape(h, w, 3)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(h, w)
+    normal = np.ascontiguousarray(normal, dtype=np.float32).reshape(h, w, 3)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32).reshape(h, w, 3)
+    kind = np.ascontiguousarray(kind, dtype=np.uint8).reshape(h, w)
+    rgb, valid, rgba = _denoise_out(w, h)
+    _check(fn(w, h, acc.ctypes.data, cnt.ctypes.data, t.ctypes.data, normal.ctypes.data, albedo.ctypes.data,
+              kind.ctypes.data, iterations, sigma_c, sigma_z, flags, rgb.ctypes.data, valid.ctypes.data,
+              rgba.ctypes.data))
+    return rgb, valid, rgba
+
+
+def denoise_planes(acc, cnt, t, normal, albedo, kind, iterations=DENOISE_DEFAULTS["iterations"],
+                   sigma_c=DENOISE_DEFAULTS["sigma_c"], sigma_z=DENOISE_DEFAULTS["sigma_z"],
+                   flags=DENOISE_DEFAULTS["flags"]):
+    """Test hook (wpt_denoise_planes): denoise()'s kernels on the caller's
+    planes; cnt is (H, W) and sizes the frame. Needs init."""
+    return _denoise_planes(lib().wpt_denoise_planes, acc, cnt, t, normal, albedo, kind, iterations, sigma_c, sigma_z,
+                           flags)
+
+
+def denoise_host(acc, cnt, t, normal, albedo, kind, iterations=DENOISE_DEFAULTS["iterations"],
+                 sigma_c=DENOISE_DEFAULTS["sigma_c"], sigma_z=DENOISE_DEFAULTS["sigma_z"],
+                 flags=DENOISE_DEFAULTS["flags"]):
+    """The filter's host restatement (wpt_denoise_host): no session, no GPU."""
+    return _denoise_planes(lib().wpt_denoise_host, acc, cnt, t, normal, albedo, kind, iterations, sigma_c, sigma_z,
+                           flags)
 
 
 def presolve_rays(rays):
