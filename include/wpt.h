@@ -428,6 +428,8 @@ int wpt_set_lanes(int32_t n);
 #define WPT_OPT_DENOISE_LDS 45   /* bit i: iteration i of wpt_denoise (step 1 << i, i = 0..2) runs the kernel that stages its tile
                                     and halo in LDS; clear: the kernel that reads its taps from global memory, as steps 8 and
                                     16 always do. The same bits either way (default 7) */
+#define WPT_OPT_HISTORY 46       /* read-only: wpt_reproject's history: 0 none, 1 usable, 2 kept in the current accumulation
+                                    (wpt_reproject is an error until the next reset) */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -522,6 +524,72 @@ int wpt_denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t
 int wpt_denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
                      const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
                      float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba);
+/* Reverse reprojection of a kept history frame into the current camera, merged
+ * with the session's frame as the calling rank holds it (partitions as in
+ * wpt_denoise). The reference resets its accumulation at every camera move
+ * (wasm_interface.rs:239-248); its materials are diffuse and emissive only, so
+ * what a surface point gathered under the previous camera is valid under the
+ * new one. Per pixel, through the first-hit planes of sample `sample` (made on
+ * the device): the hit point is projected into the history's view, the four
+ * pixels around it (bilinear weights; WPT_REPROJECT_NEAREST: the nearest one)
+ * are kept if they have samples and a finite mean, the pixel's kind (with
+ * WPT_REPROJECT_SAME_SHAPE also its shape id), a normal with n_p . n_q >=
+ * cos_min and a depth within eps_z * (distance to the history's camera); their
+ * weighted mean h enters the sums as acc + h * L, cnt + L, where L is the
+ * smallest sample count among the kept taps, at most max_len. Misses, pixels
+ * with a non-finite sum and pixels without a kept tap pass through unchanged
+ * (len 0), as every pixel does while there is no history. The definition to the
+ * operation: DESIGN.md §2; every output bit is that of wpt_reproject_host on
+ * the same planes while every finite mean and sum is at most 2^100.
+ *  acc3  3 f32  the merged sums      cnt  u32  the merged counts
+ *  len   u32    L, the history length the pixel received
+ * Any output may be NULL; with all of them NULL and no WPT_REPROJECT_KEEP
+ * nothing is launched. Without KEEP neither the session (accumulation, rounds,
+ * sample stock, wpt_stats, wpt_kernel_times) nor the history changes. With KEEP
+ * the merged frame, the planes of `sample` and the camera become the history
+ * (nothing else changes). The history outlives whatever only resets the
+ * accumulation (camera, settings, render options, partition); a new viewport,
+ * a scene upload (wpt_update_scene, a mesh reload, an option that rebuilds the
+ * scene), wpt_shutdown and wpt_history_drop drop it. A history kept in the
+ * current accumulation already contains its samples: until the next reset
+ * wpt_reproject returns WPT_ERR_INVALID_ARG and changes nothing. The intended
+ * loop: compute and reproject to display as often as wanted; reproject with
+ * KEEP once, right before wpt_update_camera; then compute and reproject again.
+ * WPT_ERR_INVALID_ARG: cos_min outside [-1, 1] or eps_z < 0 or either not
+ * finite, max_len 0 or above 2^24, an unknown flag (KEEP is one to the two
+ * plane functions); for those two also a null input, W*H == 0 or >= 2^32. */
+#define WPT_REPROJECT_KEEP 1u        /* session call only */
+#define WPT_REPROJECT_NEAREST 2u
+#define WPT_REPROJECT_SAME_SHAPE 4u
+int wpt_reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
+                  uint32_t* cnt, uint32_t* len);
+int wpt_history_drop(void);
+/* wpt_denoise's filter over the merged frame and the guide planes that the
+ * last successful wpt_reproject of this viewport left on the device: preview =
+ * reproject + filter without a host round trip. Arguments, outputs and errors
+ * as wpt_denoise; every output bit is that of wpt_denoise_host on that call's
+ * acc3 / cnt and the first-hit planes of its `sample`. WPT_ERR_INVALID_ARG also
+ * if no such call was made since the viewport was set. */
+int wpt_denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                       uint8_t* rgba);
+/* Test hook: the same kernel and launch geometry on a caller's W x H planes, in
+ * buffers of its own, no state kept. cam3: the current camera's position; acc3,
+ * cnt as wpt_read_radiance gives them; dir3, t, id, normal3, kind as
+ * wpt_first_hit does; prev_cam5 = {x, y, z, rot_x, rot_y} and the h_ planes:
+ * the history. Needs wpt_init. */
+int wpt_reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                         const float* dir3, const float* t, const int32_t* id, const float* normal3,
+                         const uint8_t* kind, const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt,
+                         const float* h_t, const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind,
+                         float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3_out,
+                         uint32_t* cnt_out, uint32_t* len_out);
+/* Host only (no session, no GPU): the restatement, the same functions the
+ * kernel calls. */
+int wpt_reproject_host(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                       const float* dir3, const float* t, const int32_t* id, const float* normal3, const uint8_t* kind,
+                       const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt, const float* h_t,
+                       const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind, float cos_min, float eps_z,
+                       uint32_t max_len, uint32_t flags, float* acc3_out, uint32_t* cnt_out, uint32_t* len_out);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */

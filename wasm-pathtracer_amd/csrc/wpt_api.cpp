@@ -6,6 +6,7 @@
 // Here the session holds the same host-side state plus one wpt::Renderer
 // that owns the GPU side; every reference `panic!` becomes a WPT_ERR_* code.
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -23,7 +24,8 @@ using namespace wpt;
 
 namespace {
 
-#include "wpt_denoise.h"  // the host part: the restatement wpt_denoise_host runs
+#include "wpt_denoise.h"    // the host part: the restatement wpt_denoise_host runs
+#include "wpt_reproject.h"  // likewise wpt_reproject_host's
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -870,6 +872,88 @@ int wpt_denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* 
   if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
   if (const char* e = denoise_plane_args(W, H, acc3, cnt, t, normal3, albedo3, kind)) return fail(WPT_ERR_INVALID_ARG, e);
   denoise_host(W, H, acc3, cnt, t, normal3, albedo3, kind, iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba);
+  return WPT_OK;
+}
+
+namespace {
+// the argument rules the reprojection entry points share; KEEP is the session call's alone
+const char* reproject_args(float cos_min, float eps_z, uint32_t max_len, uint32_t flags, uint32_t known) {
+  if (!dn_finite(cos_min) || !(cos_min >= -1.0f) || !(cos_min <= 1.0f)) return "reproject: cos_min must be in [-1, 1]";
+  if (!dn_finite(eps_z) || !(eps_z >= 0.0f)) return "reproject: eps_z must be finite and >= 0";
+  if (max_len == 0 || max_len > kRpMaxLen) return "reproject: max_len 1..2^24";
+  if (flags & ~known) return "reproject: unknown flag";
+  return nullptr;
+}
+const char* reproject_plane_args(uint32_t W, uint32_t H, std::initializer_list<const void*> in) {
+  for (const void* p : in)
+    if (!p) return "null pointer";
+  if ((uint64_t)W * H == 0 || (uint64_t)W * H >= (1ull << 32)) return "bad frame size";
+  return nullptr;
+}
+constexpr uint32_t kRpPlaneFlags = WPT_REPROJECT_NEAREST | WPT_REPROJECT_SAME_SHAPE;
+}  // namespace
+
+int wpt_reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
+                  uint32_t* cnt, uint32_t* len) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = reproject_args(cos_min, eps_z, max_len, flags, kRpPlaneFlags | WPT_REPROJECT_KEEP))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  if (g_session->renderer.history_state() == 2)
+    return fail(WPT_ERR_INVALID_ARG, "reproject: the history already holds this accumulation");
+  std::string err;
+  if (!g_session->renderer.reproject(sample, cos_min, eps_z, max_len, flags, acc3, cnt, len, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_history_drop(void) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  g_session->renderer.history_drop();
+  return WPT_OK;
+}
+
+int wpt_denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                       uint8_t* rgba) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (!g_session->renderer.has_merged())
+    return fail(WPT_ERR_INVALID_ARG, "denoise_merged: no wpt_reproject since the viewport was set");
+  std::string err;
+  if (!g_session->renderer.denoise_merged(iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                         const float* dir3, const float* t, const int32_t* id, const float* normal3,
+                         const uint8_t* kind, const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt,
+                         const float* h_t, const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind,
+                         float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3_out,
+                         uint32_t* cnt_out, uint32_t* len_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = reproject_args(cos_min, eps_z, max_len, flags, kRpPlaneFlags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = reproject_plane_args(W, H, {cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt,
+                                                  h_t, h_id, h_normal3, h_kind}))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.reproject_planes(W, H, cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt,
+                                            h_t, h_id, h_normal3, h_kind, cos_min, eps_z, max_len, flags, acc3_out,
+                                            cnt_out, len_out, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_reproject_host(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                       const float* dir3, const float* t, const int32_t* id, const float* normal3, const uint8_t* kind,
+                       const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt, const float* h_t,
+                       const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind, float cos_min, float eps_z,
+                       uint32_t max_len, uint32_t flags, float* acc3_out, uint32_t* cnt_out, uint32_t* len_out) {
+  if (const char* e = reproject_args(cos_min, eps_z, max_len, flags, kRpPlaneFlags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = reproject_plane_args(W, H, {cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt,
+                                                  h_t, h_id, h_normal3, h_kind}))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  reproject_host(W, H, cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt, h_t, h_id, h_normal3,
+                 h_kind, cos_min, eps_z, max_len, flags, acc3_out, cnt_out, len_out);
   return WPT_OK;
 }
 

@@ -330,6 +330,27 @@ class Renderer {
                       const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
                       float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba,
                       std::string& err);
+  // reverse reprojection of the kept history into the current camera, merged
+  // with the session's frame (wpt_reproject.h, wpt_reproject); a null output is
+  // not written. keep: the merged frame, the planes of `sample` and the camera
+  // become the history. The caller checks history_state() != 2 first.
+  bool reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
+                 uint32_t* cnt, uint32_t* len, std::string& err);
+  // test hook: k_reproject and its launch geometry on a caller's planes
+  bool reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                        const float* dir3, const float* t, const int32_t* id, const float* normal3,
+                        const uint8_t* kind, const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt,
+                        const float* h_t, const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind,
+                        float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3_out,
+                        uint32_t* cnt_out, uint32_t* len_out, std::string& err);
+  // the a-trous filter over the merged frame and the guide planes the last
+  // reproject of this viewport left on the device (wpt_denoise_merged)
+  bool has_merged() const { return rp_merged_; }
+  bool denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                      uint8_t* rgba, std::string& err);
+  // WPT_OPT_HISTORY: 0 no history, 1 usable, 2 kept in the current accumulation
+  int history_state() const { return hist_cur_ < 0 ? 0 : hist_epoch_ == epoch_ ? 2 : 1; }
+  void history_drop() { hist_cur_ = -1; }
   // test hook: presolve_ray on the device over caller-given rays
   bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
   // test hook: presolve_shadow on the device over caller-given {p, q} pairs
@@ -691,6 +712,19 @@ class Renderer {
               const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
               float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
   uint32_t dn_lds_ = 7;  // WPT_OPT_DENOISE_LDS
+  // Reprojection. epoch_ counts the resets of the accumulation (reset() is the
+  // one place each passes through); a history kept at the current epoch already
+  // holds the current samples. d_hist_: the two kept frames, ping-ponged (a
+  // keeping call reads one and writes the other), hist_cur_ the live one or -1;
+  // d_rp_: the merged frame and the guide planes of the last call. All made on
+  // first use and freed with the viewport.
+  uint64_t epoch_ = 0, hist_epoch_ = 0;
+  int hist_cur_ = -1;
+  float hist_cam_[5] = {0, 0, 0, 0, 0};
+  void* d_hist_[2] = {nullptr, nullptr};
+  void* d_rp_ = nullptr;
+  bool rp_merged_ = false;
+  void free_reproject();
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];
   int lanes_made_ = 0;

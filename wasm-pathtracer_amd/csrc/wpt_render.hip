@@ -2551,6 +2551,8 @@ inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kB
 #include "wpt_first_hit.h"
 #define WPT_DENOISE_KERNELS
 #include "wpt_denoise.h"
+#define WPT_REPROJECT_KERNELS
+#include "wpt_reproject.h"
 
 }  // namespace
 
@@ -2680,6 +2682,7 @@ Renderer::~Renderer() {
   if (d_fh_) (void)hipFree(d_fh_);
   if (d_fh_spill_) (void)hipFree(d_fh_spill_);
   if (d_dn_) (void)hipFree(d_dn_);
+  free_reproject();
   for (PathSet& L : lanes_) {
     if (L.counts) (void)hipFree(L.counts);
     if (L.h_counts) (void)hipHostFree(L.h_counts);
@@ -2769,6 +2772,7 @@ bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
   HIP_OK(hipStreamSynchronize(stream_));
   free_photons();
   free_scene();
+  history_drop();  // its surface points are the old scene's
   if (sc.num_inf > (uint32_t)kMaxInf && sc.use_bvh) { err = "too many infinite shapes"; return false; }
   if (sc.use_bvh && sc.depth >= (uint32_t)kMaxBvhDepth) { err = "BVH deeper than supported"; return false; }
   const size_t ns = sc.shapes.size();
@@ -3021,7 +3025,8 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 29:
     case 41:
     case 43:
-    case 44: err = "read-only option"; return false;
+    case 44:
+    case 46: err = "read-only option"; return false;
     case 24:
       if (!range(1, kMaxLanes - kAsyncLane0 - 1)) return false;  // the fill lane follows them
       if (!drain_async(err)) return false;
@@ -3085,6 +3090,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 42: v = stock_ranks_ ? 1 : 0; return true;
     case 43: v = (int64_t)ring_bytes(); return true;
     case 44: v = (int64_t)w_ | ((int64_t)h_ << 32); return true;  // read-only: the viewport
+    case 46: v = history_state(); return true;                    // read-only: the kept history
     default: return false;
   }
 }
@@ -3105,6 +3111,7 @@ bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
   if (d_dn_) (void)hipFree(d_dn_);
   d_acc_ = nullptr; d_cnt_ = nullptr; d_rgba_ = nullptr; d_samp_ = nullptr;
   d_dn_ = nullptr; dn_cap_ = 0;
+  free_reproject();
   HIP_OK(hipMalloc(&d_acc_, sizeof(float4) * (size_t)w * h));
   HIP_OK(hipMalloc(&d_cnt_, sizeof(uint32_t) * (size_t)w * h));
   HIP_OK(hipMalloc(&d_rgba_, 4 * (size_t)w * h));
@@ -3212,6 +3219,7 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
 bool Renderer::reset(std::string& err) {
   // refills in flight belong to the image being dropped
   if (!drain_async(err)) return false;
+  epoch_++;  // a history kept before this no longer holds the accumulation's samples
   next_path_ = 0;
   for (HalfRounds& r : rounds_) r.pos = r.total = r.idx = 0;
   if (!stream_ || !d_acc_) return true;
@@ -5582,6 +5590,216 @@ bool Renderer::denoise_planes(uint32_t W, uint32_t H, const float* acc3, const u
   HIP_OK(hipStreamSynchronize(stream_));
   return dn_run(W, H, d_acc, d_cnt, d_t, d_n, d_al, d_kind, scratch, iterations, sigma_c, sigma_z, flags, rgb3, valid,
                 rgba, err);
+}
+
+// ---------------------------------------------------------------------------
+// Reprojection of a kept frame (wpt_reproject.h)
+// ---------------------------------------------------------------------------
+
+namespace {
+// Parts of np pixels, each 256 B aligned: a kept frame's planes, and the merged
+// frame with the guide planes dn_run reads.
+struct RpSlices {
+  size_t at = 0, np;
+  explicit RpSlices(size_t n) : np(n) {}
+  size_t take(size_t elem) {
+    const size_t o = at;
+    at += (elem * np + 255) / 256 * 256;
+    return o;
+  }
+};
+struct RpHistLayout {
+  size_t k, r0, r1, id, bytes;
+  explicit RpHistLayout(size_t np) {
+    RpSlices z(np);
+    r0 = z.take(16); r1 = z.take(16); k = z.take(4); id = z.take(4);
+    bytes = z.at;
+  }
+  RpHist at(void* base) const {
+    char* b = (char*)base;
+    RpHist h;
+    h.k = (uint32_t*)(b + k); h.r0 = (float4*)(b + r0); h.r1 = (float4*)(b + r1); h.id = (int32_t*)(b + id);
+    return h;
+  }
+};
+struct RpMergedLayout {
+  size_t acc, cnt, len, t, normal, albedo, kind, bytes;
+  explicit RpMergedLayout(size_t np) {
+    RpSlices z(np);
+    acc = z.take(16); cnt = z.take(4); len = z.take(4); t = z.take(4); normal = z.take(12); albedo = z.take(12);
+    kind = z.take(1);
+    bytes = z.at;
+  }
+};
+const RpHist kNoHist = {nullptr, nullptr, nullptr, nullptr};
+}  // namespace
+
+void Renderer::free_reproject() {
+  for (void*& p : d_hist_) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  if (d_rp_) (void)hipFree(d_rp_);
+  d_rp_ = nullptr;
+  hist_cur_ = -1;
+  rp_merged_ = false;
+}
+
+// The session's frame as this rank holds it, merged with the kept history
+// through k_first_hit's planes of `sample`, which stay on the device; on lane
+// 0's stream like the filter, neither timed nor counted. The frame, the counts,
+// the rounds, the stock and the counters are only read. The merged frame and
+// the guide planes stay in d_rp_ for denoise_merged.
+bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
+                         uint32_t* cnt, uint32_t* len, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
+  const bool keep = (flags & kRpKeep) != 0;
+  if (!acc3 && !cnt && !len && !keep) return true;
+  const bool need_id = keep || ((flags & kRpSameShape) && hist_cur_ >= 0);
+  size_t off[7];
+  if (!first_hit_launch(sample, kFhDir | kFhT | kFhNormal | kFhAlbedo | kFhKind | (need_id ? kFhId : 0u), off, err))
+    return false;
+  const size_t np = (size_t)w_ * h_;
+  const RpMergedLayout M(np);
+  const RpHistLayout HL(np);
+  if (!d_rp_) HIP_OK(hipMalloc(&d_rp_, M.bytes));
+  const int into = hist_cur_ == 0 ? 1 : 0;  // the kept frame not being read
+  if (keep && !d_hist_[into]) HIP_OK(hipMalloc(&d_hist_[into], HL.bytes));
+  rp_merged_ = false;
+  const char* fh = (const char*)d_fh_;
+  char* m = (char*)d_rp_;
+  RpParams P;
+  P.A.W = w_; P.A.H = h_;
+  P.A.cam = mk(cam_[0], cam_[1], cam_[2]);
+  P.A.V = rp_view(w_, h_, hist_cam_);
+  P.A.cos_min = cos_min; P.A.eps_z = eps_z; P.A.max_len = max_len; P.A.flags = flags;
+  P.npix = (uint32_t)np;
+  P.acc = d_acc_;
+  P.cnt = d_cnt_;
+  P.dir = (const float*)(fh + off[0]);
+  P.t = (const float*)(fh + off[1]);
+  P.id = need_id ? (const int32_t*)(fh + off[2]) : nullptr;
+  P.normal = (const float*)(fh + off[4]);
+  P.kind = (const uint8_t*)(fh + off[6]);
+  P.hist = hist_cur_ >= 0 ? HL.at(d_hist_[hist_cur_]) : kNoHist;
+  P.acc_out = (float4*)(m + M.acc);
+  P.cnt_out = (uint32_t*)(m + M.cnt);
+  P.len_out = (uint32_t*)(m + M.len);
+  P.keep = keep ? HL.at(d_hist_[into]) : kNoHist;
+  hipStream_t s = lane0_ctx(false).stream;
+  k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
+  HIP_OK(hipGetLastError());
+  // the guides of this call, out of first_hit's buffer before its next user
+  HIP_OK(hipMemcpyAsync(m + M.t, fh + off[1], 4 * np, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(m + M.normal, fh + off[4], 12 * np, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(m + M.albedo, fh + off[5], 12 * np, hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemcpyAsync(m + M.kind, fh + off[6], np, hipMemcpyDeviceToDevice, s));
+  std::vector<float4> a4(acc3 ? np : 0);
+  if (acc3) HIP_OK(hipMemcpyAsync(a4.data(), P.acc_out, sizeof(float4) * np, hipMemcpyDeviceToHost, s));
+  if (cnt) HIP_OK(hipMemcpyAsync(cnt, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
+  if (len) HIP_OK(hipMemcpyAsync(len, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < a4.size(); i++) {
+    acc3[3 * i] = a4[i].x;
+    acc3[3 * i + 1] = a4[i].y;
+    acc3[3 * i + 2] = a4[i].z;
+  }
+  rp_merged_ = true;
+  if (keep) {
+    hist_cur_ = into;
+    hist_epoch_ = epoch_;
+    memcpy(hist_cam_, cam_, sizeof hist_cam_);
+  }
+  return true;
+}
+
+bool Renderer::denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
+                              uint8_t* valid, uint8_t* rgba, std::string& err) {
+  if (!rp_merged_ || !d_rp_) { err = "no merged frame"; return false; }
+  if (!rgb3 && !valid && !rgba) return true;
+  const size_t np = (size_t)w_ * h_;
+  const size_t need = dn_bytes(np);
+  if (need > dn_cap_) {
+    if (d_dn_) (void)hipFree(d_dn_);
+    d_dn_ = nullptr;
+    dn_cap_ = 0;
+    HIP_OK(hipMalloc(&d_dn_, need));
+    dn_cap_ = need;
+  }
+  const RpMergedLayout M(np);
+  const char* m = (const char*)d_rp_;
+  return dn_run(w_, h_, (const float4*)(m + M.acc), (const uint32_t*)(m + M.cnt), (const float*)(m + M.t),
+                (const float*)(m + M.normal), (const float*)(m + M.albedo), (const uint8_t*)(m + M.kind), (char*)d_dn_,
+                iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err);
+}
+
+// The history's planes are packed on the host with rp_pack, the function a
+// keeping k_reproject packs them with.
+bool Renderer::reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
+                                const float* dir3, const float* t, const int32_t* id, const float* normal3,
+                                const uint8_t* kind, const float* prev_cam5, const float* h_acc3,
+                                const uint32_t* h_cnt, const float* h_t, const int32_t* h_id, const float* h_normal3,
+                                const uint8_t* h_kind, float cos_min, float eps_z, uint32_t max_len, uint32_t flags,
+                                float* acc3_out, uint32_t* cnt_out, uint32_t* len_out, std::string& err) {
+  if (!stream_) { err = "no device"; return false; }
+  if (!acc3_out && !cnt_out && !len_out) return true;
+  const size_t np = (size_t)W * H;
+  const RpHistLayout HL(np);
+  HookScratch S;
+  float4* d_acc = S.d<float4>(2 * np);  // in, then out
+  uint32_t* d_cnt = S.d<uint32_t>(3 * np);  // in, out, len
+  float* d_dir = S.d<float>(3 * np);
+  float* d_t = S.d<float>(np);
+  int32_t* d_id = S.d<int32_t>(np);
+  float* d_n = S.d<float>(3 * np);
+  uint8_t* d_kind = S.d<uint8_t>(np);
+  char* d_h = S.d<char>(HL.bytes);
+  if (!S.ok) { err = "hipMalloc failed (reproject_planes)"; return false; }
+  std::vector<float4> a4(np);
+  std::vector<char> hb(HL.bytes, 0);
+  const RpHist hh = HL.at(hb.data());
+  for (size_t i = 0; i < np; i++) {
+    a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
+    const RpKept k = rp_pack(mk(h_acc3[3 * i], h_acc3[3 * i + 1], h_acc3[3 * i + 2]), h_cnt[i]);
+    hh.k[i] = (uint32_t)h_kind[i] | (k.valid ? 0x100u : 0u);
+    hh.r0[i] = make_float4(k.c.x, k.c.y, k.c.z, u2f(h_cnt[i]));
+    hh.r1[i] = make_float4(h_normal3[3 * i], h_normal3[3 * i + 1], h_normal3[3 * i + 2], h_t[i]);
+    hh.id[i] = h_id[i];
+  }
+  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, 4 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_dir, dir3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_t, t, 4 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_id, id, 4 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_h, hb.data(), HL.bytes, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  RpParams P;
+  P.A.W = W; P.A.H = H;
+  P.A.cam = mk(cam3[0], cam3[1], cam3[2]);
+  P.A.V = rp_view(W, H, prev_cam5);
+  P.A.cos_min = cos_min; P.A.eps_z = eps_z; P.A.max_len = max_len; P.A.flags = flags;
+  P.npix = (uint32_t)np;
+  P.acc = d_acc; P.cnt = d_cnt; P.dir = d_dir; P.t = d_t; P.id = d_id; P.normal = d_n; P.kind = d_kind;
+  P.hist = HL.at(d_h);
+  P.acc_out = d_acc + np; P.cnt_out = d_cnt + np; P.len_out = d_cnt + 2 * np;
+  P.keep = kNoHist;
+  hipStream_t s = lane0_ctx(false).stream;
+  k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
+  HIP_OK(hipGetLastError());
+  if (acc3_out) HIP_OK(hipMemcpyAsync(a4.data(), P.acc_out, sizeof(float4) * np, hipMemcpyDeviceToHost, s));
+  if (cnt_out) HIP_OK(hipMemcpyAsync(cnt_out, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
+  if (len_out) HIP_OK(hipMemcpyAsync(len_out, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (acc3_out)
+    for (size_t i = 0; i < np; i++) {
+      acc3_out[3 * i] = a4[i].x;
+      acc3_out[3 * i + 1] = a4[i].y;
+      acc3_out[3 * i + 2] = a4[i].z;
+    }
+  return true;
 }
 
 bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out,

@@ -358,7 +358,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
            "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41,
            "stock_ranks": 42, "stock_ring_bytes": 43, "viewport": 44,
-           "denoise_lds": 45}
+           "denoise_lds": 45, "history": 46}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -518,6 +518,85 @@ def denoise_host(acc, cnt, t, normal, albedo, kind, iterations=DENOISE_DEFAULTS[
     """The filter's host restatement (wpt_denoise_host): no session, no GPU."""
     return _denoise_planes(lib().wpt_denoise_host, acc, cnt, t, normal, albedo, kind, iterations, sigma_c, sigma_z,
                            flags)
+
+
+REPROJECT_KEEP, REPROJECT_NEAREST, REPROJECT_SAME_SHAPE = 1, 2, 4  # WPT_REPROJECT_*
+# the documented defaults of reproject(): see profiles/reproject/README.md
+REPROJECT_DEFAULTS = {"cos_min": 0.9, "eps_z": 0.05, "max_len": 64, "flags": 0}
+
+
+def reproject(sample=0, cos_min=REPROJECT_DEFAULTS["cos_min"], eps_z=REPROJECT_DEFAULTS["eps_z"],
+              max_len=REPROJECT_DEFAULTS["max_len"], flags=REPROJECT_DEFAULTS["flags"]):
+    """The session's frame merged with the kept history reprojected into the
+    current camera (wpt_reproject), through the first-hit planes of sample
+    `sample`: (acc (H, W, 3) f32, cnt (H, W) u32, len (H, W) u32). With
+    REPROJECT_KEEP the merged frame becomes the history: call it once, right
+    before update_camera. Without it nothing of the session changes."""
+    vp = get_option("viewport")
+    w, h = vp & 0xFFFFFFFF, vp >> 32
+    acc = np.empty((h, w, 3), dtype=np.float32)
+    cnt = np.empty((h, w), dtype=np.uint32)
+    ln = np.empty((h, w), dtype=np.uint32)
+    _check(lib().wpt_reproject(sample, cos_min, eps_z, max_len, flags, acc.ctypes.data, cnt.ctypes.data,
+                               ln.ctypes.data))
+    return acc, cnt, ln
+
+
+def history_drop():
+    """Forget reproject()'s kept history (wpt_history_drop)."""
+    _check(lib().wpt_history_drop())
+
+
+def denoise_merged(iterations=DENOISE_DEFAULTS["iterations"], sigma_c=DENOISE_DEFAULTS["sigma_c"],
+                   sigma_z=DENOISE_DEFAULTS["sigma_z"], flags=DENOISE_DEFAULTS["flags"]):
+    """denoise()'s filter over the merged frame and guide planes the last
+    reproject() left on the device (wpt_denoise_merged): (rgb, valid, rgba)."""
+    vp = get_option("viewport")
+    rgb, valid, rgba = _denoise_out(vp & 0xFFFFFFFF, vp >> 32)
+    _check(lib().wpt_denoise_merged(iterations, sigma_c, sigma_z, flags, rgb.ctypes.data, valid.ctypes.data,
+                                    rgba.ctypes.data))
+    return rgb, valid, rgba
+
+
+def _reproject_planes(fn, cam, cur, prev_cam, hist, cos_min, eps_z, max_len, flags):
+    acc, cnt, dirs, t, ids, normal, kind = cur
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    h, w = cnt.shape
+
+    def f3(a):
+        return np.ascontiguousarray(a, dtype=np.float32).reshape(h, w, 3)
+
+    def p1(a, dt):
+        return np.ascontiguousarray(a, dtype=dt).reshape(h, w)
+
+    h_acc, h_cnt, h_t, h_id, h_normal, h_kind = hist
+    ins = [np.ascontiguousarray(cam, dtype=np.float32).reshape(-1)[:3].copy(), f3(acc), cnt, f3(dirs),
+           p1(t, np.float32), p1(ids, np.int32), f3(normal), p1(kind, np.uint8),
+           np.ascontiguousarray(prev_cam, dtype=np.float32).reshape(5), f3(h_acc), p1(h_cnt, np.uint32),
+           p1(h_t, np.float32), p1(h_id, np.int32), f3(h_normal), p1(h_kind, np.uint8)]
+    acc_o = np.empty((h, w, 3), dtype=np.float32)
+    cnt_o = np.empty((h, w), dtype=np.uint32)
+    len_o = np.empty((h, w), dtype=np.uint32)
+    _check(fn(w, h, *[a.ctypes.data for a in ins], cos_min, eps_z, max_len, flags, acc_o.ctypes.data,
+              cnt_o.ctypes.data, len_o.ctypes.data))
+    return acc_o, cnt_o, len_o
+
+
+def reproject_planes(cam, cur, prev_cam, hist, cos_min=REPROJECT_DEFAULTS["cos_min"],
+                     eps_z=REPROJECT_DEFAULTS["eps_z"], max_len=REPROJECT_DEFAULTS["max_len"],
+                     flags=REPROJECT_DEFAULTS["flags"]):
+    """Test hook (wpt_reproject_planes): reproject()'s kernel on the caller's
+    planes. cam: the current camera (its position is used); cur = (acc, cnt, dir,
+    t, id, normal, kind), cnt (H, W) sizing the frame; prev_cam = (x, y, z, rot_x,
+    rot_y) and hist = (acc, cnt, t, id, normal, kind): the history. Needs init."""
+    return _reproject_planes(lib().wpt_reproject_planes, cam, cur, prev_cam, hist, cos_min, eps_z, max_len, flags)
+
+
+def reproject_host(cam, cur, prev_cam, hist, cos_min=REPROJECT_DEFAULTS["cos_min"],
+                   eps_z=REPROJECT_DEFAULTS["eps_z"], max_len=REPROJECT_DEFAULTS["max_len"],
+                   flags=REPROJECT_DEFAULTS["flags"]):
+    """Reprojection's host restatement (wpt_reproject_host): no session, no GPU."""
+    return _reproject_planes(lib().wpt_reproject_host, cam, cur, prev_cam, hist, cos_min, eps_z, max_len, flags)
 
 
 def presolve_rays(rays):
