@@ -430,6 +430,8 @@ int wpt_set_lanes(int32_t n);
                                     16 always do. The same bits either way (default 7) */
 #define WPT_OPT_HISTORY 46       /* read-only: wpt_reproject's history: 0 none, 1 usable, 2 kept in the current accumulation
                                     (wpt_reproject is an error until the next reset) */
+#define WPT_OPT_MAP_MODE 47      /* read-only: 1 once wpt_compute_map traced a sample in the current accumulation (wpt_compute is
+                                    an error until the next reset), else 0 */
 #define WPT_OPT_LOG 34           /* 1: host steps of adaptive rounds / the stock to stderr (debugging; default 0) */
 #define WPT_OPT_SCENE_TRAVERSAL 28 /* read-only (wpt_get_option): what the session's scene runs: 0 exact BVH2, 1 BVH4, 2 linear
                                       scan (BVH disabled), -1 no scene */
@@ -590,6 +592,70 @@ int wpt_reproject_host(uint32_t W, uint32_t H, const float* cam3, const float* a
                        const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt, const float* h_t,
                        const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind, float cos_min, float eps_z,
                        uint32_t max_len, uint32_t flags, float* acc3_out, uint32_t* cnt_out, uint32_t* len_out);
+/* Guided sampling, the planning half: a sample map (width*height u32, raster
+ * order) from the session's counts cnt, the history length len that the last
+ * successful wpt_reproject since the last reset of the accumulation gave each
+ * pixel (0 everywhere if there was none) and the partition. Per pixel, with
+ * e = min(cnt + len, 2^32 - 1):
+ *   need = 0 outside the calling rank's partition;
+ *   with WPT_MAP_MISS_ONCE, where sample `sample`'s primary ray misses (the
+ *     first-hit kind, made on the device): 1 if cnt == 0, else 0 (a caller's
+ *     approximation, off by default: `sample` is read under this flag only);
+ *   otherwise min(target > e ? target - e : 0, max_per_pixel).
+ * T = the sum of the needs. With budget == 0 or T <= budget, count = need.
+ * Otherwise the budget is dealt in proportion, exactly: with P the exclusive
+ * prefix of the needs in raster order, count[p] = floor(P[p+1] * budget / T) -
+ * floor(P[p] * budget / T) in u64. Then the counts sum to budget, count <= need,
+ * and count == 0 where need == 0. All of it is integer arithmetic: every output
+ * bit is that of wpt_sample_map_host on the same planes.
+ *  count_out  width*height u32 (may be NULL)
+ *  total_out  2 u64: {T, the sum of the counts} (may be NULL)
+ * The map stays on the device for wpt_compute_map until the accumulation is
+ * reset (camera, settings, render options, partition, viewport, scene). The
+ * session (accumulation, rounds, sample stock, wpt_stats, wpt_kernel_times,
+ * history) is not touched. WPT_ERR_INVALID_ARG: target 0, max_per_pixel 0, an
+ * unknown flag, T >= 2^32 (lower max_per_pixel; no map is kept); for the two
+ * functions below also a null input, W*H == 0 or >= 2^32 - 1. The definition to
+ * the operation: DESIGN.md §2. */
+#define WPT_MAP_MISS_ONCE 1u
+int wpt_sample_map(uint32_t sample, uint32_t target, uint32_t max_per_pixel, uint32_t budget, uint32_t flags,
+                   uint32_t* count_out, uint64_t* total_out);
+/* Test hook: the same kernels and launch geometry on a caller's W x H planes
+ * (cnt as wpt_read_radiance gives it, len as wpt_reproject does, kind as
+ * wpt_first_hit does, member: u8, 1 for the pixels of the partition), in buffers
+ * of its own, no state kept. Needs wpt_init. */
+int wpt_sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                          const uint8_t* member, uint32_t target, uint32_t max_per_pixel, uint32_t budget,
+                          uint32_t flags, uint32_t* count_out, uint64_t* total_out);
+/* Host only (no session, no GPU): the restatement, the same functions the
+ * kernels call. */
+int wpt_sample_map_host(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                        const uint8_t* member, uint32_t target, uint32_t max_per_pixel, uint32_t budget, uint32_t flags,
+                        uint32_t* count_out, uint64_t* total_out);
+/* Guided sampling, the tracing half: traces a sample map. count: width*height
+ * u32 in raster order, or NULL for the map the last successful wpt_sample_map
+ * of the current accumulation left on the device (none: WPT_ERR_INVALID_ARG).
+ * Every pixel p of the calling rank's partition, in partition order, gets the
+ * samples s = cnt[p] .. cnt[p] + count[p] - 1 (cnt as wpt_read_radiance gives
+ * it): paths path_seed(frame_seed, p, s) with the render type of p's screen
+ * half, the session's depth cap and light-debug setting, added to the pixel's
+ * sum in sample order after what it holds; its count grows by count[p]. Entries
+ * of other ranks' pixels are ignored; several ranks need no collective. This is
+ * exact at any moment of a session, because every producer of samples leaves a
+ * pixel holding exactly the samples 0 .. cnt - 1. The call first waits for the
+ * sample stock's refills in flight, as wpt_sync does; the stock is not read
+ * again. The frame is the same bits for every batch size, lane count and launch
+ * option; wpt_stats and wpt_kernel_times count the paths and rays as any
+ * batch's; PNEE halves build or reuse the session's octree as wpt_compute does.
+ * Map mode: a call that traced at least one sample puts the session into map
+ * mode (WPT_OPT_MAP_MODE reads 1). The random and adaptive sequences take their
+ * sample indices from round and position counters, not from the counts, so
+ * until the next reset of the accumulation wpt_compute returns
+ * WPT_ERR_INVALID_ARG and changes nothing; further maps may be traced. A map of
+ * zeros succeeds, launches nothing and does not enter map mode.
+ * WPT_ERR_INVALID_ARG, with nothing traced: the partition's counts sum to more
+ * than 2^32 - 1, or a pixel's cnt + count exceeds 2^32 - 1. */
+int wpt_compute_map(const uint32_t* count);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */

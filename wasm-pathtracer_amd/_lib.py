@@ -73,6 +73,10 @@ _SIGS = {
     "wpt_denoise_merged": (ctypes.c_int, [c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
     "wpt_reproject_planes": (ctypes.c_int, [c_u32, c_u32] + [c_p] * 15 + [c_f32, c_f32, c_u32, c_u32, c_p, c_p, c_p]),
     "wpt_reproject_host": (ctypes.c_int, [c_u32, c_u32] + [c_p] * 15 + [c_f32, c_f32, c_u32, c_u32, c_p, c_p, c_p]),
+    "wpt_sample_map": (ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
+    "wpt_sample_map_planes": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
+    "wpt_sample_map_host": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
+    "wpt_compute_map": (ctypes.c_int, [c_p]),
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),

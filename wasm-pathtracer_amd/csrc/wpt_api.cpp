@@ -26,6 +26,7 @@ namespace {
 
 #include "wpt_denoise.h"    // the host part: the restatement wpt_denoise_host runs
 #include "wpt_reproject.h"  // likewise wpt_reproject_host's
+#include "wpt_guided.h"     // and wpt_sample_map_host's
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -314,6 +315,12 @@ int wpt_notify_texture_loaded(uint32_t) {
 int wpt_compute(size_t num_samples) {
   if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
   std::string err;
+  // a map's samples start at each pixel's count; the sequences below take their
+  // sample indices from round and position counters and would repeat them
+  if (g_session->renderer.map_mode())
+    return fail(WPT_ERR_INVALID_ARG,
+                "compute: the session is in map mode (wpt_compute_map traced a sample map) until the accumulation "
+                "is reset");
   if (!g_session->renderer.compute((uint64_t)num_samples, err)) return fail(WPT_ERR_DEVICE, err);
   return WPT_OK;
 }
@@ -954,6 +961,66 @@ int wpt_reproject_host(uint32_t W, uint32_t H, const float* cam3, const float* a
     return fail(WPT_ERR_INVALID_ARG, e);
   reproject_host(W, H, cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt, h_t, h_id, h_normal3,
                  h_kind, cos_min, eps_z, max_len, flags, acc3_out, cnt_out, len_out);
+  return WPT_OK;
+}
+
+namespace {
+// the argument rules the sample map's entry points share
+const char* sample_map_args(uint32_t target, uint32_t max_per_pixel, uint32_t flags) {
+  if (target == 0) return "sample_map: target must be > 0";
+  if (max_per_pixel == 0) return "sample_map: max_per_pixel must be > 0";
+  if (flags & ~(uint32_t)WPT_MAP_MISS_ONCE) return "sample_map: unknown flag";
+  return nullptr;
+}
+const char* sample_map_plane_args(uint32_t W, uint32_t H, std::initializer_list<const void*> in) {
+  for (const void* p : in)
+    if (!p) return "null pointer";
+  if ((uint64_t)W * H == 0 || (uint64_t)W * H >= 0xFFFFFFFFull) return "bad frame size";
+  return nullptr;
+}
+}  // namespace
+
+int wpt_sample_map(uint32_t sample, uint32_t target, uint32_t max_per_pixel, uint32_t budget, uint32_t flags,
+                   uint32_t* count_out, uint64_t* total_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = sample_map_args(target, max_per_pixel, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  bool invalid = false;
+  if (!g_session->renderer.sample_map(sample, target, max_per_pixel, budget, flags, count_out, total_out, invalid, err))
+    return fail(invalid ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                          const uint8_t* member, uint32_t target, uint32_t max_per_pixel, uint32_t budget,
+                          uint32_t flags, uint32_t* count_out, uint64_t* total_out) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = sample_map_args(target, max_per_pixel, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = sample_map_plane_args(W, H, {cnt, len, kind, member})) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  bool invalid = false;
+  if (!g_session->renderer.sample_map_planes(W, H, cnt, len, kind, member, target, max_per_pixel, budget, flags,
+                                             count_out, total_out, invalid, err))
+    return fail(invalid ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_sample_map_host(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                        const uint8_t* member, uint32_t target, uint32_t max_per_pixel, uint32_t budget, uint32_t flags,
+                        uint32_t* count_out, uint64_t* total_out) {
+  if (const char* e = sample_map_args(target, max_per_pixel, flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = sample_map_plane_args(W, H, {cnt, len, kind, member})) return fail(WPT_ERR_INVALID_ARG, e);
+  if (!sample_map_host(W, H, cnt, len, kind, member, target, max_per_pixel, budget, flags, count_out, total_out))
+    return fail(WPT_ERR_INVALID_ARG, "sample_map: the needs sum to 2^32 or more (lower max_per_pixel)");
+  return WPT_OK;
+}
+
+int wpt_compute_map(const uint32_t* count) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  std::string err;
+  bool invalid = false;
+  if (!g_session->renderer.compute_map(count, invalid, err))
+    return fail(invalid ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
   return WPT_OK;
 }
 

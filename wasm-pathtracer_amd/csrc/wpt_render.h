@@ -351,6 +351,22 @@ class Renderer {
   // WPT_OPT_HISTORY: 0 no history, 1 usable, 2 kept in the current accumulation
   int history_state() const { return hist_cur_ < 0 ? 0 : hist_epoch_ == epoch_ ? 2 : 1; }
   void history_drop() { hist_cur_ = -1; }
+  // Guided sampling (wpt_guided.h). sample_map: the map planned from the
+  // counts, the len plane of this accumulation's last reproject and (under
+  // WPT_MAP_MISS_ONCE) the first-hit kinds of `sample`; it stays on the device
+  // for compute_map(nullptr). compute_map: pixel p of the partition gets
+  // count[p] samples from sample cnt[p] on. `invalid`: the failure is the
+  // caller's argument (WPT_ERR_INVALID_ARG), nothing was traced or kept.
+  bool sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
+                  uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err);
+  // test hook: the same kernels and launch geometry on a caller's planes
+  bool sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                         const uint8_t* member, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
+                         uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err);
+  bool compute_map(const uint32_t* count, bool& invalid, std::string& err);
+  // WPT_OPT_MAP_MODE: a map was traced in this accumulation (wpt_compute is an
+  // error until the next reset)
+  bool map_mode() const { return map_mode_; }
   // test hook: presolve_ray on the device over caller-given rays
   bool presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out, std::string& err);
   // test hook: presolve_shadow on the device over caller-given {p, q} pairs
@@ -724,7 +740,25 @@ class Renderer {
   void* d_hist_[2] = {nullptr, nullptr};
   void* d_rp_ = nullptr;
   bool rp_merged_ = false;
+  uint64_t rp_epoch_ = 0;  // the accumulation d_rp_'s len plane belongs to (sample_map reads it in that one only)
   void free_reproject();
+  // Guided sampling. d_map_: sample_map's scratch and the map it leaves (made
+  // on first use, freed with the viewport), valid in the accumulation map_epoch_
+  // while map_ok_; d_mplan_: compute_map's uploaded map, offsets, bases, scan
+  // sums and words (freed with the partition). map_mode_: reset() clears it.
+  void* d_map_ = nullptr;
+  bool map_ok_ = false;
+  uint64_t map_epoch_ = 0;
+  void* d_mplan_ = nullptr;
+  bool map_mode_ = false;
+  void free_guided();
+  // the kernels of sample_map over device planes (null len / kind / member: see
+  // k_map_need) in a scratch of MapLayout(np); T comes back, the deal is
+  // launched only if it is below 2^32
+  bool map_run(uint32_t np, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind, const uint8_t* member,
+               char* scratch, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags, uint32_t* count_out,
+               uint64_t* total_out, bool& invalid, std::string& err);
+  bool compute_end(std::string& err);  // what every tracing call ends with: counts, overflow flag, work counters
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];
   int lanes_made_ = 0;

@@ -2553,6 +2553,8 @@ inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kB
 #include "wpt_denoise.h"
 #define WPT_REPROJECT_KERNELS
 #include "wpt_reproject.h"
+#define WPT_GUIDED_KERNELS
+#include "wpt_guided.h"
 
 }  // namespace
 
@@ -2683,6 +2685,7 @@ Renderer::~Renderer() {
   if (d_fh_spill_) (void)hipFree(d_fh_spill_);
   if (d_dn_) (void)hipFree(d_dn_);
   free_reproject();
+  free_guided();
   for (PathSet& L : lanes_) {
     if (L.counts) (void)hipFree(L.counts);
     if (L.h_counts) (void)hipHostFree(L.h_counts);
@@ -3026,7 +3029,8 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 41:
     case 43:
     case 44:
-    case 46: err = "read-only option"; return false;
+    case 46:
+    case 47: err = "read-only option"; return false;
     case 24:
       if (!range(1, kMaxLanes - kAsyncLane0 - 1)) return false;  // the fill lane follows them
       if (!drain_async(err)) return false;
@@ -3091,6 +3095,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 43: v = (int64_t)ring_bytes(); return true;
     case 44: v = (int64_t)w_ | ((int64_t)h_ << 32); return true;  // read-only: the viewport
     case 46: v = history_state(); return true;                    // read-only: the kept history
+    case 47: v = map_mode_ ? 1 : 0; return true;                  // read-only: a sample map was traced
     default: return false;
   }
 }
@@ -3140,6 +3145,7 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
   half_npix_[0] = half_npix_[1] = 0;
   if (d_xidx_) { (void)hipFree(d_xidx_); d_xidx_ = nullptr; }
   maxpart_ = 0;
+  free_guided();
   if (w_ && h_ && nranks > 1) {
     tile_partition(w_, h_, rank, nranks, tile, part_pix_);
     if (!part_pix_.empty()) {
@@ -3220,6 +3226,7 @@ bool Renderer::reset(std::string& err) {
   // refills in flight belong to the image being dropped
   if (!drain_async(err)) return false;
   epoch_++;  // a history kept before this no longer holds the accumulation's samples
+  map_mode_ = false;  // (a kept sample map and the len plane end with their epoch)
   next_path_ = 0;
   for (HalfRounds& r : rounds_) r.pos = r.total = r.idx = 0;
   if (!stream_ || !d_acc_) return true;
@@ -3672,7 +3679,9 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
       if (!launch_shadow(C, C.ps->sh_count(B.b - 1), nullptr, err)) return false;
     }
   }
-  const bool round = B.half >= 0 && !B.moff;
+  // a sample round, or an explicit mapping that is not a stock batch (a sample
+  // map, compute_map): a pixel's paths are consecutive, L.pixel its entry
+  const bool round = B.half >= 0 || B.moff;
   const uint32_t npix = B.part ? B.npix : (uint32_t)part_pix_.size();
   const uint32_t* part = B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
   // in-order accumulation: lane i's slice after lane i-1's (each pixel's
@@ -4440,6 +4449,11 @@ bool Renderer::compute(uint64_t num_paths, std::string& err) {
     next_path_ += n;
     done += n;
   }
+  return compute_end(err);
+}
+
+// The end of a tracing call (compute, compute_map).
+bool Renderer::compute_end(std::string& err) {
   // every lane's work of this call done (an adaptive round's batch returns
   // without waiting): the readbacks below go through the null stream
   if (!flush_counts(err)) return false;
@@ -5706,6 +5720,7 @@ bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t m
     acc3[3 * i + 2] = a4[i].z;
   }
   rp_merged_ = true;
+  rp_epoch_ = epoch_;
   if (keep) {
     hist_cur_ = into;
     hist_epoch_ = epoch_;
@@ -5800,6 +5815,213 @@ bool Renderer::reproject_planes(uint32_t W, uint32_t H, const float* cam3, const
       acc3_out[3 * i + 2] = a4[i].z;
     }
   return true;
+}
+
+// ---------------------------------------------------------------------------
+// Guided sampling (wpt_guided.h)
+// ---------------------------------------------------------------------------
+
+namespace {
+// sample_map's scratch for np pixels: the needs and their scan (np + 1 u64),
+// the chunk sums, the map itself and the membership plane
+struct MapLayout {
+  size_t pre, sums, count, member, bytes;
+  uint32_t nb;
+  explicit MapLayout(size_t np) {
+    nb = (uint32_t)((np + 1 + kScanChunk - 1) / kScanChunk);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    pre = 0;
+    sums = pre + up(8 * (np + 1));
+    count = sums + up(8 * ((size_t)nb + 1));
+    member = count + up(4 * np);
+    bytes = member + up(np);
+  }
+};
+// compute_map's plan for a partition of npart of np pixels: the uploaded map,
+// the offsets (npart + 1) and bases, the scan's chunk sums, k_map_plan's words
+struct MapPlanLayout {
+  size_t in, off, base, sums, words, bytes;
+  uint32_t nb;
+  MapPlanLayout(size_t np, size_t npart) {
+    nb = (uint32_t)((npart + 1 + kScanChunk - 1) / kScanChunk);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    in = 0;
+    off = in + up(4 * np);
+    base = off + up(4 * (npart + 1));
+    sums = base + up(4 * npart);
+    words = sums + up(4 * ((size_t)nb + 1));
+    bytes = words + 256;
+  }
+};
+}  // namespace
+
+void Renderer::free_guided() {
+  if (d_map_) (void)hipFree(d_map_);
+  if (d_mplan_) (void)hipFree(d_mplan_);
+  d_map_ = nullptr;
+  d_mplan_ = nullptr;
+  map_ok_ = false;
+}
+
+// Needs, their scan, T back to the host, then the deal: on lane 0's stream like
+// the filter and the reprojection, neither timed nor counted.
+bool Renderer::map_run(uint32_t np, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
+                       const uint8_t* member, char* scratch, uint32_t target, uint32_t max_pp, uint32_t budget,
+                       uint32_t flags, uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err) {
+  const MapLayout L(np);
+  u64* pre = (u64*)(scratch + L.pre);
+  u64* sums = (u64*)(scratch + L.sums);
+  uint32_t* count = (uint32_t*)(scratch + L.count);
+  const uint32_t n = np + 1;
+  hipStream_t s = lane0_ctx(false).stream;
+  k_map_need<<<blocks_for(n), kBlock, 0, s>>>(np, cnt, len, kind, member, target, max_pp, flags, pre);
+  k_scan64_local<<<L.nb, kBlock, 0, s>>>(pre, n, sums);
+  k_scan64_sums<<<1, kBlock, 0, s>>>(sums, L.nb);
+  k_scan64_add<<<L.nb, kBlock, 0, s>>>(pre, n, sums);
+  HIP_OK(hipGetLastError());
+  uint64_t T = 0;
+  HIP_OK(hipMemcpyAsync(&T, pre + np, sizeof T, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (total_out) { total_out[0] = T; total_out[1] = 0; }
+  if (T >= (1ull << 32)) {
+    invalid = true;
+    err = "sample_map: the needs sum to 2^32 or more (lower max_per_pixel)";
+    return false;
+  }
+  k_map_deal<<<blocks_for(np), kBlock, 0, s>>>(np, pre, budget, count);
+  HIP_OK(hipGetLastError());
+  if (count_out) HIP_OK(hipMemcpyAsync(count_out, count, 4 * (size_t)np, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (total_out) total_out[1] = map_dealt(budget, T);
+  return true;
+}
+
+// The session's map: its counts, the len plane the last reproject of this
+// accumulation left in d_rp_ (else 0 everywhere), k_first_hit's kinds of
+// `sample` where the flags read them, the partition's membership. The frame,
+// the rounds, the stock, the counters and the history are only read.
+bool Renderer::sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
+                          uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err) {
+  invalid = false;
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
+  const size_t np = (size_t)w_ * h_;
+  const uint8_t* kind = nullptr;
+  if (flags & kMapMissOnce) {
+    size_t off[7];
+    if (!first_hit_launch(sample, kFhKind, off, err)) return false;
+    kind = (const uint8_t*)d_fh_ + off[6];
+  }
+  const MapLayout L(np);
+  if (!d_map_) HIP_OK(hipMalloc(&d_map_, L.bytes));
+  map_ok_ = false;
+  char* m = (char*)d_map_;
+  const uint8_t* member = nullptr;
+  if (nranks_ > 1) {
+    std::vector<uint8_t> mb(np, 0);
+    for (uint32_t p : part_pix_) mb[p] = 1;
+    HIP_OK(hipMemcpyAsync(m + L.member, mb.data(), np, hipMemcpyHostToDevice, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    member = (const uint8_t*)(m + L.member);
+  }
+  const uint32_t* len = nullptr;
+  if (rp_merged_ && d_rp_ && rp_epoch_ == epoch_) len = (const uint32_t*)((const char*)d_rp_ + RpMergedLayout(np).len);
+  if (!map_run((uint32_t)np, d_cnt_, len, kind, member, m, target, max_pp, budget, flags, count_out, total_out, invalid,
+               err))
+    return false;
+  map_ok_ = true;
+  map_epoch_ = epoch_;
+  return true;
+}
+
+bool Renderer::sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len,
+                                 const uint8_t* kind, const uint8_t* member, uint32_t target, uint32_t max_pp,
+                                 uint32_t budget, uint32_t flags, uint32_t* count_out, uint64_t* total_out,
+                                 bool& invalid, std::string& err) {
+  invalid = false;
+  if (!stream_) { err = "no device"; return false; }
+  const size_t np = (size_t)W * H;
+  HookScratch S;
+  uint32_t* d_cnt = S.d<uint32_t>(2 * np);  // cnt, len
+  uint8_t* d_km = S.d<uint8_t>(2 * np);     // kind, member
+  char* d_s = S.d<char>(MapLayout(np).bytes);
+  if (!S.ok) { err = "hipMalloc failed (sample_map_planes)"; return false; }
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, 4 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_cnt + np, len, 4 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_km, kind, np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_km + np, member, np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return map_run((uint32_t)np, d_cnt, d_cnt + np, d_km, d_km + np, d_s, target, max_pp, budget, flags, count_out,
+                 total_out, invalid, err);
+}
+
+// Traces a sample map: partition entry p's pixel gets count[pixel] samples from
+// sample cnt[pixel] on. Every producer of samples leaves a pixel holding
+// exactly samples 0 .. cnt - 1 (a random half mid-round, an adaptive round,
+// k_consume, the progressive order of several ranks), so cnt is the next unused
+// index at any moment of a session. The batches are run_batch's with an
+// explicit mapping that is no stock batch: k_generate* find a position's entry
+// by binary search in the offsets, k_accumulate_round adds a pixel's paths in
+// sample order, lane after lane, so a pixel may straddle lanes and batches.
+bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& err) {
+  invalid = false;
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (!d_acc_ || part_pix_.empty()) { err = "no viewport"; return false; }
+  if (!count && !(map_ok_ && d_map_ && map_epoch_ == epoch_)) {
+    invalid = true;
+    err = "compute_map: no sample map of this accumulation on the device (wpt_sample_map)";
+    return false;
+  }
+  // refills and fill batches in flight write the ring only; the ring is not
+  // read again before the next reset drops it (map mode)
+  if (!sync(err)) return false;
+  const size_t np = (size_t)w_ * h_;
+  const uint32_t npart = (uint32_t)part_pix_.size();
+  const MapPlanLayout L(np, npart);
+  if (!d_mplan_) HIP_OK(hipMalloc(&d_mplan_, L.bytes));
+  char* m = (char*)d_mplan_;
+  uint32_t* off = (uint32_t*)(m + L.off);
+  uint32_t* base = (uint32_t*)(m + L.base);
+  uint32_t* sums = (uint32_t*)(m + L.sums);
+  u64* words = (u64*)(m + L.words);
+  const uint32_t* src = (const uint32_t*)(m + L.in);
+  if (count) HIP_OK(hipMemcpyAsync(m + L.in, count, 4 * np, hipMemcpyHostToDevice, stream_));
+  else src = (const uint32_t*)((const char*)d_map_ + MapLayout(np).count);
+  HIP_OK(hipMemsetAsync(words, 0, 2 * sizeof(u64), stream_));
+  k_map_plan<<<blocks_for((uint64_t)npart + 1), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, npart, src,
+                                                                     d_cnt_, off, base, words);
+  HIP_OK(hipGetLastError());
+  uint64_t hw[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (hw[1]) { invalid = true; err = "compute_map: a pixel's sample index would pass 2^32 - 1"; return false; }
+  if (hw[0] > 0xFFFFFFFFull) { invalid = true; err = "compute_map: the map's counts sum to more than 2^32 - 1"; return false; }
+  const uint64_t total = hw[0];
+  if (total == 0) return true;
+  const uint32_t n = npart + 1;
+  k_scan_local<<<L.nb, kBlock, 0, stream_>>>(off, n, sums);
+  k_scan_sums<<<1, kBlock, 0, stream_>>>(sums, L.nb);
+  k_scan_add<<<L.nb, kBlock, 0, stream_>>>(off, n, sums);
+  HIP_OK(hipGetLastError());
+  const uint64_t bsz = std::min<uint64_t>(std::max<uint64_t>(batch_, 1), 0xFFFFFFFFull);
+  if ((left_type_ == 2 || right_type_ == 2) && !build_photons(err)) return false;
+  {
+    // the lanes' capacity, as compute() sizes it
+    const int ml = main_lanes();
+    const uint64_t want = std::min(bsz, total);
+    const uint64_t per = (want + ml - 1) / ml;
+    for (int i = 0; i < ml; i++)
+      if (!ensure_lane(i, (i == 0 && want < (uint64_t)ml * kMinLanePaths) ? want : per, err)) return false;
+  }
+  Batch M;
+  M.moff = off;
+  M.mbase = base;
+  M.nent = npart;
+  map_mode_ = true;
+  const uint64_t cap = std::max<uint64_t>(std::min(batch_cap(), bsz), 1);
+  for (uint64_t k0 = 0; k0 < total; k0 += cap)
+    if (!run_batch(k0, std::min<uint64_t>(cap, total - k0), -1, err, nullptr, 0, &M)) return false;
+  return compute_end(err);
 }
 
 bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out,

@@ -358,7 +358,7 @@ OPTIONS = {"defaults": 0, "traversal": 1, "traversal_sh": 2, "fused": 3, "fused_
            "log": 34, "stock_prefill": 35, "async_fused_below": 36, "presolve": 37, "drop_miss": 38,
            "presolve_shadow": 39, "gen_shade": 40, "oct_view": 41,
            "stock_ranks": 42, "stock_ring_bytes": 43, "viewport": 44,
-           "denoise_lds": 45, "history": 46}
+           "denoise_lds": 45, "history": 46, "map_mode": 47}
 # symbolic values of the enumerated options
 # traversal: exact BVH2, the BVH4 fast path, or auto (the default: BVH4 on
 # scenes with other shapes than triangles, else BVH2)
@@ -597,6 +597,67 @@ def reproject_host(cam, cur, prev_cam, hist, cos_min=REPROJECT_DEFAULTS["cos_min
                    flags=REPROJECT_DEFAULTS["flags"]):
     """Reprojection's host restatement (wpt_reproject_host): no session, no GPU."""
     return _reproject_planes(lib().wpt_reproject_host, cam, cur, prev_cam, hist, cos_min, eps_z, max_len, flags)
+
+
+MAP_MISS_ONCE = 1  # WPT_MAP_MISS_ONCE: a pixel whose ray of `sample` misses needs one sample only
+
+
+def sample_map(sample=0, target=8, max_per_pixel=8, budget=0, flags=0):
+    """A sample map planned from the session's counts and the history length
+    the last reproject() of this accumulation recovered (wpt_sample_map):
+    (count (H, W) u32, (T, dealt)). A pixel needs min(target - min(cnt + len,
+    2^32 - 1), max_per_pixel) samples (0 outside the partition); T is the sum
+    of the needs; budget 0 or >= T gives every pixel its need, a smaller one is
+    dealt in proportion, exactly. The map stays on the device for
+    compute_map(None); the session is not touched."""
+    vp = get_option("viewport")
+    w, h = vp & 0xFFFFFFFF, vp >> 32
+    count = np.empty((h, w), dtype=np.uint32)
+    tot = np.zeros(2, dtype=np.uint64)
+    _check(lib().wpt_sample_map(sample, target, max_per_pixel, budget, flags, count.ctypes.data, tot.ctypes.data))
+    return count, (int(tot[0]), int(tot[1]))
+
+
+def compute_map(count=None):
+    """Traces a sample map (wpt_compute_map): pixel p of this rank's partition
+    gets count[p] samples starting at its sample count. None: the map the last
+    sample_map() of this accumulation left on the device. Once a map traced a
+    sample, compute() is an error until the accumulation is reset
+    (get_option("map_mode") reads 1)."""
+    if count is None:
+        _check(lib().wpt_compute_map(None))
+        return
+    vp = get_option("viewport")
+    w, h = vp & 0xFFFFFFFF, vp >> 32
+    c = np.ascontiguousarray(count, dtype=np.uint32).reshape(h, w)
+    _check(lib().wpt_compute_map(c.ctypes.data))
+
+
+def _sample_map_planes(fn, cnt, length, kind, member, target, max_per_pixel, budget, flags):
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    h, w = cnt.shape
+    length = np.ascontiguousarray(length, dtype=np.uint32).reshape(h, w)
+    kind = np.ascontiguousarray(kind, dtype=np.uint8).reshape(h, w)
+    member = np.ascontiguousarray(member, dtype=np.uint8).reshape(h, w)
+    count = np.empty((h, w), dtype=np.uint32)
+    tot = np.zeros(2, dtype=np.uint64)
+    _check(fn(w, h, cnt.ctypes.data, length.ctypes.data, kind.ctypes.data, member.ctypes.data, target, max_per_pixel,
+              budget, flags, count.ctypes.data, tot.ctypes.data))
+    return count, (int(tot[0]), int(tot[1]))
+
+
+def sample_map_planes(cnt, length, kind, member, target=8, max_per_pixel=8, budget=0, flags=0):
+    """Test hook (wpt_sample_map_planes): sample_map()'s kernels on the caller's
+    planes; cnt is (H, W) and sizes the frame, member is 1 for the pixels of the
+    partition. Needs init."""
+    return _sample_map_planes(lib().wpt_sample_map_planes, cnt, length, kind, member, target, max_per_pixel, budget,
+                              flags)
+
+
+def sample_map_host(cnt, length, kind, member, target=8, max_per_pixel=8, budget=0, flags=0):
+    """The sample map's host restatement (wpt_sample_map_host): no session, no GPU."""
+    return _sample_map_planes(lib().wpt_sample_map_host, cnt, length, kind, member, target, max_per_pixel, budget,
+                              flags)
 
 
 def presolve_rays(rays):
