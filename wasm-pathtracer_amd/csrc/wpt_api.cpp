@@ -48,9 +48,8 @@ struct Session {
   // multi-GPU (wpt_set_comm): the RCCL communicator, the packed partition of
   // this rank and the gathered partitions of all ranks (rank-major)
   Comm* comm = nullptr;
-  float4* comm_send = nullptr;
-  float4* comm_recv = nullptr;
-  uint64_t comm_slot = 0;
+  DevBuf<float4> comm_send;  // comm_send.cap() float4: the slot of every rank
+  DevBuf<float4> comm_recv;
   // or a caller's transport (wpt_set_transport) over caller-owned buffers
   wpt_transport_fn xfer = nullptr;
   void* xfer_user = nullptr;
@@ -72,10 +71,8 @@ struct Session {
     xfer_slot = 0;
     comm_destroy(comm);
     comm = nullptr;
-    if (comm_send) (void)hipFree(comm_send);
-    if (comm_recv) (void)hipFree(comm_recv);
-    comm_send = comm_recv = nullptr;
-    comm_slot = 0;
+    comm_send.reset();
+    comm_recv.reset();
   }
 };
 
@@ -448,7 +445,7 @@ namespace {
 int comm_exchange(void* user) {
   Session& s = *(Session*)user;
   std::string err;
-  if (!comm_allgather(s.comm, s.comm_send, s.comm_recv, s.comm_slot, s.renderer.stream(), err)) {
+  if (!comm_allgather(s.comm, s.comm_send, s.comm_recv, s.comm_send.cap(), s.renderer.stream(), err)) {
     g_err = err;
     return 1;
   }
@@ -460,18 +457,16 @@ int comm_exchange(void* user) {
 bool size_comm(Session& s) {
   uint64_t slot = std::max<uint64_t>(s.renderer.exchange_slot(), s.renderer.part_pixels());
   if (slot == 0) slot = 1;
-  if (slot > s.comm_slot) {
-    if (s.comm_send) (void)hipFree(s.comm_send);
-    if (s.comm_recv) (void)hipFree(s.comm_recv);
-    s.comm_send = s.comm_recv = nullptr;
-    s.comm_slot = 0;
-    if (hipMalloc(&s.comm_send, sizeof(float4) * slot) != hipSuccess ||
-        hipMalloc(&s.comm_recv, sizeof(float4) * slot * comm_size(s.comm)) != hipSuccess)
+  if (slot > s.comm_send.cap()) {
+    s.comm_send.reset();
+    s.comm_recv.reset();
+    if (s.comm_send.alloc(slot) != hipSuccess || s.comm_recv.alloc(slot * comm_size(s.comm)) != hipSuccess) {
+      s.comm_send.reset();  // (its capacity is the slot both buffers hold)
       return false;
-    s.comm_slot = slot;
+    }
   }
   // adaptive rounds exchange the frame over the communicator
-  s.renderer.set_exchange(comm_exchange, &s, s.comm_send, s.comm_recv, s.comm_slot);
+  s.renderer.set_exchange(comm_exchange, &s, s.comm_send, s.comm_recv, s.comm_send.cap());
   return true;
 }
 }  // namespace
@@ -518,10 +513,10 @@ int wpt_gather_frame(uint32_t root) {
   if (root >= comm_size(s.comm)) return fail(WPT_ERR_INVALID_ARG, "bad root");
   if (!size_comm(s)) return fail(WPT_ERR_DEVICE, "hipMalloc failed (communicator buffers)");
   std::string err;
-  if (!s.renderer.copy_partition((float*)s.comm_send, err)) return fail(WPT_ERR_DEVICE, err);
-  if (!comm_gather(s.comm, s.comm_send, s.comm_recv, s.comm_slot, root, s.renderer.stream(), err))
+  if (!s.renderer.copy_partition((float*)s.comm_send.get(), err)) return fail(WPT_ERR_DEVICE, err);
+  if (!comm_gather(s.comm, s.comm_send, s.comm_recv, s.comm_send.cap(), root, s.renderer.stream(), err))
     return fail(WPT_ERR_DEVICE, err);
-  if (comm_rank(s.comm) == root && !s.renderer.unpack_ranks(s.comm_recv, s.comm_slot, err))
+  if (comm_rank(s.comm) == root && !s.renderer.unpack_ranks(s.comm_recv, s.comm_send.cap(), err))
     return fail(WPT_ERR_DEVICE, err);
   return WPT_OK;
 }

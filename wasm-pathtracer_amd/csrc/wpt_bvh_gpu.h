@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "wpt_devmem.h"
 #include "wpt_scene.h"
 
 namespace wpt {
@@ -50,26 +51,23 @@ class BvhGpu : public Bvh2Builder {
   void release();
   hipStream_t stream_ = nullptr;
   size_t cap_ = 0;
-  float* d_box_ = nullptr;
-  float* d_loc_ = nullptr;
-  uint32_t* d_ord_[2] = {nullptr, nullptr};
-  uint32_t* d_key_[2] = {nullptr, nullptr};
-  uint32_t* d_seg_ = nullptr;
-  uint8_t* d_bin_ = nullptr;
+  DevBuf<float> d_box_, d_loc_;
+  DevBuf<uint32_t> d_ord_[2], d_key_[2];
+  DevBuf<uint32_t> d_seg_;
+  DevBuf<uint8_t> d_bin_;
   // per task (at most 2n - 1): range, parent box, result
-  uint32_t* d_toff_ = nullptr;
-  uint32_t* d_tcnt_ = nullptr;
-  uint32_t* d_tchild_ = nullptr;  // first child task (0: leaf)
-  uint32_t* d_tdepth_ = nullptr;
-  uint32_t* d_tsplit_ = nullptr;  // left count of a split task
-  float* d_tpbox_ = nullptr;      // 6 per task: the box subdivide() receives
-  float* d_tbox_ = nullptr;       // 6 per task: the node's box
+  DevBuf<uint32_t> d_toff_, d_tcnt_;
+  DevBuf<uint32_t> d_tchild_;  // first child task (0: leaf)
+  DevBuf<uint32_t> d_tdepth_;
+  DevBuf<uint32_t> d_tsplit_;  // left count of a split task
+  DevBuf<float> d_tpbox_;      // 6 per task: the box subdivide() receives
+  DevBuf<float> d_tbox_;       // 6 per task: the node's box
   // per task of the current level
-  uint32_t* d_vmm_ = nullptr;     // 2 per task: ordered keys of min / max centroid
-  uint32_t* d_bins_ = nullptr;    // 16 x 7 per task: box keys (6) and count
-  uint32_t* d_ntask_ = nullptr;   // task counter
-  uint32_t* h_ntask_ = nullptr;   // pinned mirror
-  void* d_tmp_ = nullptr;
+  DevBuf<uint32_t> d_vmm_;     // 2 per task: ordered keys of min / max centroid
+  DevBuf<uint32_t> d_bins_;    // 16 x 7 per task: box keys (6) and count
+  DevBuf<uint32_t> d_ntask_;   // task counter
+  PinBuf<uint32_t> h_ntask_;   // pinned mirror
+  DevBuf<char> d_tmp_;         // the radix sort's temporary storage
   size_t tmp_bytes_ = 0;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   double last_ms_ = 0.0;

@@ -276,27 +276,22 @@ uint32_t blocks(size_t n) { return (uint32_t)std::max<size_t>(1, (n + kB - 1) / 
 
 }  // namespace
 
+// The buffers go before the stream: the members' own destructors run too late.
 BvhGpu::~BvhGpu() {
   release();
+  h_ntask_.reset();
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
-  if (h_ntask_) (void)hipHostFree(h_ntask_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 void BvhGpu::release() {
-  void* bufs[] = {d_box_, d_loc_, d_ord_[0], d_ord_[1], d_key_[0], d_key_[1], d_seg_, d_bin_, d_toff_,
-                  d_tcnt_, d_tchild_, d_tdepth_, d_tsplit_, d_tpbox_, d_tbox_, d_vmm_, d_bins_, d_ntask_, d_tmp_};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  d_box_ = d_loc_ = nullptr;
-  d_ord_[0] = d_ord_[1] = d_key_[0] = d_key_[1] = nullptr;
-  d_seg_ = nullptr;
-  d_bin_ = nullptr;
-  d_toff_ = d_tcnt_ = d_tchild_ = d_tdepth_ = d_tsplit_ = nullptr;
-  d_tpbox_ = d_tbox_ = nullptr;
-  d_vmm_ = d_bins_ = d_ntask_ = nullptr;
-  d_tmp_ = nullptr;
+  for (DevBuf<float>* b : {&d_box_, &d_loc_, &d_tpbox_, &d_tbox_}) b->reset();
+  for (DevBuf<uint32_t>* b : {&d_ord_[0], &d_ord_[1], &d_key_[0], &d_key_[1], &d_seg_, &d_toff_, &d_tcnt_, &d_tchild_,
+                              &d_tdepth_, &d_tsplit_, &d_vmm_, &d_bins_, &d_ntask_})
+    b->reset();
+  d_bin_.reset();
+  d_tmp_.reset();
   tmp_bytes_ = 0;
   cap_ = 0;
 }
@@ -306,32 +301,32 @@ bool BvhGpu::reserve(size_t n, std::string& err) {
     BVH_OK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     BVH_OK(hipEventCreate(&ev0_));
     BVH_OK(hipEventCreate(&ev1_));
-    BVH_OK(hipHostMalloc(&h_ntask_, sizeof(uint32_t)));
+    BVH_OK(h_ntask_.alloc(1));
   }
   if (n <= cap_) return true;
   release();
   const size_t nt = 2 * n;  // tasks: at most 2n - 1 nodes
-  BVH_OK(hipMalloc(&d_box_, sizeof(float) * 6 * n));
-  BVH_OK(hipMalloc(&d_loc_, sizeof(float) * 3 * n));
+  BVH_OK(d_box_.alloc(6 * n));
+  BVH_OK(d_loc_.alloc(3 * n));
   for (int k = 0; k < 2; k++) {
-    BVH_OK(hipMalloc(&d_ord_[k], sizeof(uint32_t) * n));
-    BVH_OK(hipMalloc(&d_key_[k], sizeof(uint32_t) * n));
+    BVH_OK(d_ord_[k].alloc(n));
+    BVH_OK(d_key_[k].alloc(n));
   }
-  BVH_OK(hipMalloc(&d_seg_, sizeof(uint32_t) * n));
-  BVH_OK(hipMalloc(&d_bin_, n));
-  BVH_OK(hipMalloc(&d_toff_, sizeof(uint32_t) * nt));
-  BVH_OK(hipMalloc(&d_tcnt_, sizeof(uint32_t) * nt));
-  BVH_OK(hipMalloc(&d_tchild_, sizeof(uint32_t) * nt));
-  BVH_OK(hipMalloc(&d_tdepth_, sizeof(uint32_t) * nt));
-  BVH_OK(hipMalloc(&d_tsplit_, sizeof(uint32_t) * nt));
-  BVH_OK(hipMalloc(&d_tpbox_, sizeof(float) * 6 * nt));
-  BVH_OK(hipMalloc(&d_tbox_, sizeof(float) * 6 * nt));
-  BVH_OK(hipMalloc(&d_vmm_, sizeof(uint32_t) * 2 * n));
-  BVH_OK(hipMalloc(&d_bins_, sizeof(uint32_t) * kBinWords * n));
-  BVH_OK(hipMalloc(&d_ntask_, sizeof(uint32_t)));
+  BVH_OK(d_seg_.alloc(n));
+  BVH_OK(d_bin_.alloc(n));
+  BVH_OK(d_toff_.alloc(nt));
+  BVH_OK(d_tcnt_.alloc(nt));
+  BVH_OK(d_tchild_.alloc(nt));
+  BVH_OK(d_tdepth_.alloc(nt));
+  BVH_OK(d_tsplit_.alloc(nt));
+  BVH_OK(d_tpbox_.alloc(6 * nt));
+  BVH_OK(d_tbox_.alloc(6 * nt));
+  BVH_OK(d_vmm_.alloc(2 * n));
+  BVH_OK(d_bins_.alloc(kBinWords * n));
+  BVH_OK(d_ntask_.alloc(1));
   hipcub::DoubleBuffer<uint32_t> kb(d_key_[0], d_key_[1]), vb(d_ord_[0], d_ord_[1]);
   BVH_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes_, kb, vb, (int)n, 0, 32, stream_));
-  BVH_OK(hipMalloc(&d_tmp_, tmp_bytes_));
+  BVH_OK(d_tmp_.alloc(tmp_bytes_));
   cap_ = n;
   return true;
 }

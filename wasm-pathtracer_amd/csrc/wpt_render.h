@@ -13,6 +13,7 @@
 #include <deque>
 #include <vector>
 
+#include "wpt_devmem.h"
 #include "wpt_photon.h"
 #include "wpt_scene.h"
 #include "wpt_seqsum.h"
@@ -172,22 +173,17 @@ struct PathSet {
   hipStream_t lo = nullptr;      // async batches with WPT_OPT_ASYNC_PRIO: a low-priority stream (lazily made)
   hipEvent_t done = nullptr;     // recorded after the lane's accumulation
   uint64_t cap = 0;
-  uint32_t* pixel = nullptr;     // per path: pixel (round batches: partition pixel index)
-  float4* col = nullptr;         // per path: radiance
-  float4* ro[2] = {nullptr, nullptr};
-  float4* rd[2] = {nullptr, nullptr};
-  float4* thr[2] = {nullptr, nullptr};
+  DevBuf<uint32_t> pixel;        // per path: pixel (round batches: partition pixel index)
+  DevBuf<float4> col;            // per path: radiance
+  DevBuf<float4> ro[2], rd[2], thr[2];
   // hit records of the two streams (bounce b's at [b & 1]: k_shade(b) reads
   // them while it writes the presolved rays' records of bounce b + 1)
-  float* t = nullptr;
-  int32_t* id = nullptr;
-  float* t1 = nullptr;
-  int32_t* id1 = nullptr;
-  float4 *so = nullptr, *sd = nullptr, *sc = nullptr;
-  uint32_t* counts = nullptr;    // kCountWords, see above
-  uint32_t* h_counts = nullptr;  // pinned mirror
-  uint2* spill = nullptr;       // traversal-stack spill (entries beyond the LDS slots)
-  size_t spill_cap = 0;
+  DevBuf<float> t, t1;
+  DevBuf<int32_t> id, id1;
+  DevBuf<float4> so, sd, sc;
+  DevBuf<uint32_t> counts;    // kCountWords, see above
+  PinBuf<uint32_t> h_counts;  // pinned mirror
+  DevBuf<uint2> spill;        // traversal-stack spill (entries beyond the LDS slots), spill.cap() entries
   float* hit_t(int k) const { return k ? t1 : t; }
   int32_t* hit_id(int k) const { return k ? id1 : id; }
   // count words: rays of bounce b, shadow rays of bounce b, k_shade's append
@@ -501,6 +497,9 @@ class Renderer {
   void free_scene();
   void free_paths();
   void free_photons();
+  void free_frame();       // the viewport's frame buffers and denoise's scratch
+  void free_partition();   // the pixel lists, the exchange index, compute_map's plan
+  void free_stock_side();  // the ring's side buffers and the refill pool (not the ring)
   bool upload_photons(const PhotonTree& tree, std::string& err);
   // Sample rounds, per screen half: as the reference's two RenderInstances
   // (wasm_interface.rs:90-94, :374-379), each half has its own strategy and
@@ -512,29 +511,27 @@ class Renderer {
   struct HalfRounds {
     uint64_t total = 0, pos = 0;    // positions in the current round / taken
     uint32_t idx = 0;               // rounds planned since the reset
-    uint32_t* rc = nullptr;         // samples per partition pixel -> (scan) offsets, [npix] = total
-    uint32_t* rbase = nullptr;      // samples of the pixel before the round
+    DevBuf<uint32_t> rc;            // samples per partition pixel -> (scan) offsets, [npix] = total
+    DevBuf<uint32_t> rbase;         // samples of the pixel before the round
     // several ranks: the round is planned over the whole frame (global
     // offsets gc, bases gbase); rc / rbase then hold this rank's slice
-    uint32_t* gc = nullptr;
-    uint32_t* gbase = nullptr;
+    DevBuf<uint32_t> gc, gbase;
   } rounds_[2];
   uint64_t round_cap_ = 0;
-  uint32_t* d_scan_sums_ = nullptr;
-  uint32_t* d_gsums_ = nullptr;
-  float* d_mse_[2] = {nullptr, nullptr};
-  uint32_t* d_bmm_ = nullptr;       // per-tile {min, max} error keys of a half
-  float* h_mse_[2] = {nullptr, nullptr};  // pinned copies of the per-pixel errors (host sum)
+  DevBuf<uint32_t> d_scan_sums_, d_gsums_;
+  DevBuf<float> d_mse_[2];
+  DevBuf<uint32_t> d_bmm_;          // per-tile {min, max} error keys of a half
+  PinBuf<float> h_mse_[2];          // pinned copies of the per-pixel errors (host sum)
   // the errors' sequential sum: per-chunk f64 sums / prefixes and chunk
   // effects on the device (k_sum_*), the effects' pinned copy for the walk
-  double* d_s64_ = nullptr;
-  ChunkEff* d_eff_ = nullptr;
-  ChunkEff* h_eff_ = nullptr;
-  uint32_t* d_need_ = nullptr;    // per chunk: the walk will likely re-sum it
-  uint32_t* d_list_ = nullptr;    // those chunks: count, then their indices
-  float* d_fb_ = nullptr;         // the elements of the first kSumFetch of them
-  uint32_t* h_list_ = nullptr;
-  float* h_fb_ = nullptr;
+  DevBuf<double> d_s64_;
+  DevBuf<ChunkEff> d_eff_;
+  PinBuf<ChunkEff> h_eff_;
+  DevBuf<uint32_t> d_need_;       // per chunk: the walk will likely re-sum it
+  DevBuf<uint32_t> d_list_;       // those chunks: count, then their indices
+  DevBuf<float> d_fb_;            // the elements of the first kSumFetch of them
+  PinBuf<uint32_t> h_list_;
+  PinBuf<float> h_fb_;
   // The sample stock of adaptive halves (wpt_stock.h, WPT_OPT_STOCK): a ring
   // of stock_slots_ samples per pixel of this rank's partition (radiance +
   // ray counts) and the id of the refill tracing each, the frontier per
@@ -550,13 +547,14 @@ class Renderer {
   uint32_t stock_extra_ = 8;    // WPT_OPT_STOCK_EXTRA
   uint32_t stock_every_ = 3;    // WPT_OPT_STOCK_EVERY: a refill after every this many rounds of a half
                                 // (3 vs 2: C5 +1.3 %, init defaults +0.4 %, profiles/r06/ab_stock_every3.jsonl)
+  // the ring pair stays raw: ring_take / ring_give own it across sessions
   float4* d_stock_ = nullptr;
   uint32_t* d_stock_id_ = nullptr;
   size_t stock_bytes_[2] = {0, 0};   // the two ring blocks' sizes (cached blocks may be larger)
-  uint32_t* d_front_ = nullptr;
-  uint32_t* d_def_ = nullptr;        // [npart + 1] deficit counts -> offsets, then [npart] bases
-  uint32_t* d_bmax_ = nullptr;       // per-block maxima scratch
-  unsigned long long* d_rays_ = nullptr;  // [3] consumed rays (extension, shadow) and samples, [1] unused, + scratch
+  DevBuf<uint32_t> d_front_;
+  DevBuf<uint32_t> d_def_;           // [npart + 1] deficit counts -> offsets, then [npart] bases
+  DevBuf<uint32_t> d_bmax_;          // per-block maxima scratch
+  DevBuf<unsigned long long> d_rays_;     // [3] consumed rays (extension, shadow) and samples, [1] unused, + scratch
   uint64_t stock_cap_ = 0;           // partition pixels x slots the ring holds (0: not allocated)
   uint64_t stock_frame_ = 0;         // the viewport's pixels when the ring was made (a resize orphans it)
   uint32_t stock_used_slots_ = 0;
@@ -568,13 +566,13 @@ class Renderer {
     uint32_t id = 0;
     bool live = false;
     bool counted = false;      // its batches' counts are in stats_ (stock_rays, bounces)
-    uint32_t* off = nullptr;   // [n + 1] counts -> offsets over the half's list
-    uint32_t* base = nullptr;  // [n] first sample per pixel
+    DevBuf<uint32_t> off;      // [n + 1] counts -> offsets over the half's list
+    DevBuf<uint32_t> base;     // [n] first sample per pixel
     std::deque<Batch> chunks;  // its batches (stable addresses: the queue points at them)
   };
   Refill refills_[kMaxRefill];
   hipEvent_t refill_ev_[kMaxRefill][2 * kRefillChunks] = {};
-  uint32_t* h_refill_cnt_ = nullptr;  // pinned [kMaxRefill][kRefillChunks][kCountWords + 1]
+  PinBuf<uint32_t> h_refill_cnt_;     // pinned [kMaxRefill][kRefillChunks][kCountWords + 1]
   uint32_t refill_id_ = 0;            // ids of the session's refills, in issue order
   int refill_lane_ = 0;               // the stock lane of the next refill
   uint32_t round_need_[2] = {0, 0};   // per half: 1 + the refill its current round's samples wait for (0: none)
@@ -624,14 +622,13 @@ class Renderer {
   // same-session (profiles/r06/ab_async_fused_grid.jsonl)
   int async_grid_pct_ = 100;  // WPT_OPT_ASYNC_GRID_PCT: their traversal grids, % of resident capacity (0: the main batches')
   uint64_t async_fused_below_ = 1ull << 26;  // WPT_OPT_ASYNC_FUSED_BELOW: async batches below this many paths run fused (0: fused_below)
-  uint32_t* d_seam_pix_[2] = {nullptr, nullptr};
-  uint32_t* d_rest_pix_[2] = {nullptr, nullptr};
+  DevBuf<uint32_t> d_seam_pix_[2], d_rest_pix_[2];
   uint32_t seam_npix_[2] = {0, 0}, rest_npix_[2] = {0, 0};
   static constexpr int kMaxFill = 8;
   Batch fill_[kMaxFill];
   int nfill_ = 0;
   hipEvent_t fill_ev_[kMaxFill][2] = {};
-  uint32_t* h_fill_cnt_ = nullptr;  // pinned [kMaxFill][kCountWords + 1]
+  PinBuf<uint32_t> h_fill_cnt_;     // pinned [kMaxFill][kCountWords + 1]
   bool async_pending() const { return !aq_[0].empty() || !aq_[1].empty(); }
   int fill_lane() const { return kAsyncLane0 + stock_lanes_; }
   bool issue_fill(int h, uint64_t k0, uint64_t n, std::string& err);
@@ -649,21 +646,21 @@ class Renderer {
     return async_grid_pct_ > 0 ? std::max<uint32_t>(1u, (uint32_t)((uint64_t)g * async_grid_pct_ / base_pct)) : g;
   }
   bool async_oneshot_ = false;  // WPT_OPT_ASYNC_ONESHOT
-  uint8_t* d_samp_ = nullptr;       // sampling visualisation RGBA8 (allocated with the viewport)
+  DevBuf<uint8_t> d_samp_;          // sampling visualisation RGBA8 (allocated with the viewport)
   ExchangeFn xfn_ = nullptr;
   void* xuser_ = nullptr;
   float4* xlocal_ = nullptr;
   float4* xall_ = nullptr;
   uint64_t xslot_ = 0;
   uint64_t maxpart_ = 0;             // largest partition over all ranks
-  uint32_t* d_xidx_ = nullptr;       // gathered entry -> pixel (~0: padding), nranks * maxpart_
+  DevBuf<uint32_t> d_xidx_;          // gathered entry -> pixel (~0: padding), nranks * maxpart_
   bool photons_ok_ = false;
   uint64_t photons_shot_ = 0, photons_stored_ = 0;
   std::vector<uint32_t> oct_child_;
   std::vector<float> oct_cum_;
-  uint32_t* d_oct_child_ = nullptr;
-  float* d_oct_cum_ = nullptr;
-  uint32_t* d_oct_corners_ = nullptr;
+  DevBuf<uint32_t> d_oct_child_;
+  DevBuf<float> d_oct_cum_;
+  DevBuf<uint32_t> d_oct_corners_;
 
   int device_ = -1;
   int ncu_ = 256;
@@ -706,23 +703,20 @@ class Renderer {
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
   uint32_t probe_cap_ = 0, probe_waves_ = 0, probe_used_ = 0;
-  uint4* d_probe_ = nullptr;
+  DevBuf<uint4> d_probe_;
   std::vector<uint32_t> probe_meta_;
   uint4* probe_slot(const LaunchCtx& C, int kernel, uint32_t grid);
-  uint32_t* d_fallback_ = nullptr; // [2] rays re-traced exactly (extend, shadow)
+  DevBuf<uint32_t> d_fallback_;    // [2] rays re-traced exactly (extend, shadow)
   // first_hit's own buffers, kept between calls: the overflow flag and the
   // planes; the traversal-stack spill area of its grid
-  void* d_fh_ = nullptr;
-  size_t fh_cap_ = 0;
-  uint2* d_fh_spill_ = nullptr;
-  size_t fh_spill_cap_ = 0;
+  DevBuf<char> d_fh_;
+  DevBuf<uint2> d_fh_spill_;
   // k_first_hit of the planes in `mask` into d_fh_ (plane k at off[k]); waits for it
   bool first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err);
   // denoise's scratch for the session's viewport (records A0, A1, B, a' and
   // the outputs), made on first use, freed with the viewport; the filter
   // itself over device planes in a scratch of dn_bytes(W * H)
-  void* d_dn_ = nullptr;
-  size_t dn_cap_ = 0;
+  DevBuf<char> d_dn_;
   static size_t dn_bytes(size_t np);
   bool dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
               const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
@@ -737,8 +731,8 @@ class Renderer {
   uint64_t epoch_ = 0, hist_epoch_ = 0;
   int hist_cur_ = -1;
   float hist_cam_[5] = {0, 0, 0, 0, 0};
-  void* d_hist_[2] = {nullptr, nullptr};
-  void* d_rp_ = nullptr;
+  DevBuf<char> d_hist_[2];
+  DevBuf<char> d_rp_;
   bool rp_merged_ = false;
   uint64_t rp_epoch_ = 0;  // the accumulation d_rp_'s len plane belongs to (sample_map reads it in that one only)
   void free_reproject();
@@ -746,10 +740,10 @@ class Renderer {
   // on first use, freed with the viewport), valid in the accumulation map_epoch_
   // while map_ok_; d_mplan_: compute_map's uploaded map, offsets, bases, scan
   // sums and words (freed with the partition). map_mode_: reset() clears it.
-  void* d_map_ = nullptr;
+  DevBuf<char> d_map_;
   bool map_ok_ = false;
   uint64_t map_epoch_ = 0;
-  void* d_mplan_ = nullptr;
+  DevBuf<char> d_mplan_;
   bool map_mode_ = false;
   void free_guided();
   // the kernels of sample_map over device planes (null len / kind / member: see
@@ -771,7 +765,7 @@ class Renderer {
   int nlanes_ = 4;                 // wpt_set_lanes (1..kMaxLanes); 4 with half-GPU traversal grids (C3 +4.5 % over 3 lanes at full grids)
   hipEvent_t ev_main_ = nullptr;   // lanes > 0 wait for the main stream's prior work
   hipEvent_t ev_ref_ = nullptr;    // profiling: time origin of a batch's launch intervals
-  std::vector<void*> scene_bufs_;
+  std::vector<DevBuf<char>> scene_bufs_;
   DevScene ds_{};
   uint32_t depth_ = 0;
   bool scene_ok_ = false;
@@ -785,20 +779,20 @@ class Renderer {
 
   uint32_t rank_ = 0, nranks_ = 1, tile_ = 16;
   std::vector<uint32_t> part_pix_;
-  uint32_t* d_part_pix_ = nullptr;
+  DevBuf<uint32_t> d_part_pix_;
   // each screen half's pixels of this rank: one rank in tile order; several
   // ranks as partition entries (indices into part_pix_) in partition order
-  uint32_t* d_half_pix_[2] = {nullptr, nullptr};
-  uint32_t* d_frame_pix_ = nullptr;                // one rank: the frame's pixels, tile order
+  DevBuf<uint32_t> d_half_pix_[2];
+  DevBuf<uint32_t> d_frame_pix_;                   // one rank: the frame's pixels, tile order
   uint32_t half_npix_[2] = {0, 0};
   uint64_t next_path_ = 0;
 
-  float4* d_acc_ = nullptr;
-  uint32_t* d_cnt_ = nullptr;
-  uint8_t* d_rgba_ = nullptr;
+  DevBuf<float4> d_acc_;
+  DevBuf<uint32_t> d_cnt_;
+  DevBuf<uint8_t> d_rgba_;
 
-  unsigned long long* d_work_ = nullptr;  // [kWorkCopies][kWorkWords] extend visits/tests/node bytes, shadow visits/tests/node bytes, ...
-  uint32_t* h_word_ = nullptr;     // pinned scratch of the round planning (a round's path count)
+  DevBuf<unsigned long long> d_work_;     // [kWorkCopies][kWorkWords] extend visits/tests/node bytes, shadow visits/tests/node bytes, ...
+  PinBuf<uint32_t> h_word_;        // pinned scratch of the round planning (a round's path count)
 
   bool counting_ = false;
   bool profiling_ = false;

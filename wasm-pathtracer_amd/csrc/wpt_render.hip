@@ -2548,6 +2548,58 @@ __global__ void k_pack_partition(const uint32_t* __restrict__ part_pix, uint32_t
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
+// The exclusive u32 scan of data[0 .. n) in place, in chunks of kScanChunk:
+// `sums` holds a word per chunk. The caller checks hipGetLastError.
+inline void scan_u32(hipStream_t stream, uint32_t* data, uint32_t n, uint32_t* sums) {
+  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
+  k_scan_local<<<nb, kBlock, 0, stream>>>(data, n, sums);
+  k_scan_sums<<<1, kBlock, 0, stream>>>(sums, nb);
+  k_scan_add<<<nb, kBlock, 0, stream>>>(data, n, sums);
+}
+
+// n host rgb triples as float4 (w = 0) to dst, queued on s from `stage`, which
+// the caller keeps until it has waited for s.
+inline hipError_t upload_rgb3(hipStream_t s, const float* rgb3, size_t n, std::vector<float4>& stage, float4* dst) {
+  stage.resize(n);
+  for (size_t i = 0; i < n; i++) stage[i] = make_float4(rgb3[3 * i], rgb3[3 * i + 1], rgb3[3 * i + 2], 0.0f);
+  return hipMemcpyAsync(dst, stage.data(), sizeof(float4) * n, hipMemcpyHostToDevice, s);
+}
+
+// The xyz of n device float4 into host rgb triples: queued on s, then waits
+// for s (and with it for the copies the caller queued before). A null rgb3
+// only waits.
+inline hipError_t download_rgb3(hipStream_t s, const float4* src, size_t n, float* rgb3) {
+  std::vector<float4> a(rgb3 ? n : 0);
+  if (rgb3) {
+    const hipError_t e = hipMemcpyAsync(a.data(), src, sizeof(float4) * n, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+  }
+  const hipError_t e = hipStreamSynchronize(s);
+  for (size_t i = 0; i < a.size(); i++) {
+    rgb3[3 * i] = a[i].x;
+    rgb3[3 * i + 1] = a[i].y;
+    rgb3[3 * i + 2] = a[i].z;
+  }
+  return e;
+}
+
+// n shadow rays p -> q towards `light` as the shadow stream holds them: (origin,
+// distance) and (direction, light id), formed as Scene::shadow_ray does
+// (scene.rs:105-108).
+inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, std::vector<float4>& o,
+                             std::vector<float4>& d) {
+  o.resize(n);
+  d.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    const float* r = pq + 6 * i;
+    V3 org, dir;
+    float dl;
+    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), org, dir, dl);
+    o[i] = make_float4(org.x, org.y, org.z, dl);
+    d[i] = make_float4(dir.x, dir.y, dir.z, u2f((uint32_t)light[i]));
+  }
+}
+
 #include "wpt_first_hit.h"
 #define WPT_DENOISE_KERNELS
 #include "wpt_denoise.h"
@@ -2636,78 +2688,64 @@ static void ring_give(int dev, void* p, size_t bytes) {
 
 Renderer::Renderer() {}
 
+// Shutdown order: the async lanes drained, the device idle, the rings back to
+// their cache, every buffer released, then the events and last the streams.
+// The buffers go here and not in their members' destructors, which run after
+// this body, when the streams are gone.
 Renderer::~Renderer() {
   {
     std::string e;
     (void)drain_async(e);
   }
-  {
-    if (d_stock_ || d_stock_id_) {
-      // the rings go back to the cache once nothing reads them (hipFree
-      // would have waited for the device the same way)
-      if (stream_) (void)hipStreamSynchronize(stream_);
-      for (PathSet& L : lanes_) {
-        if (L.stream) (void)hipStreamSynchronize(L.stream);
-        if (L.lo) (void)hipStreamSynchronize(L.lo);
-      }
-      ring_give(device_, d_stock_, stock_bytes_[0]);
-      ring_give(device_, d_stock_id_, stock_bytes_[1]);
+  if (d_stock_ || d_stock_id_) {
+    // the rings go back to the cache once nothing reads them (hipFree
+    // would have waited for the device the same way)
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    for (PathSet& L : lanes_) {
+      if (L.stream) (void)hipStreamSynchronize(L.stream);
+      if (L.lo) (void)hipStreamSynchronize(L.lo);
     }
-    void* sb[] = {d_front_, d_def_, d_bmax_, d_rays_};
-    for (void* q : sb)
-      if (q) (void)hipFree(q);
-    for (Refill& f : refills_) {
-      if (f.off) (void)hipFree(f.off);
-      if (f.base) (void)hipFree(f.base);
-    }
+    ring_give(device_, d_stock_, stock_bytes_[0]);
+    ring_give(device_, d_stock_id_, stock_bytes_[1]);
   }
-  if (h_refill_cnt_) (void)hipHostFree(h_refill_cnt_);
-  for (auto& re : refill_ev_)
-    for (hipEvent_t e : re)
-      if (e) (void)hipEventDestroy(e);
+  free_stock_side();
+  h_refill_cnt_.reset();
+  h_fill_cnt_.reset();
   free_rounds();
   free_photons();
   free_scene();
   free_paths();
-  if (d_part_pix_) (void)hipFree(d_part_pix_);
-  for (uint32_t* p : d_half_pix_)
-    if (p) (void)hipFree(p);
-  if (d_frame_pix_) (void)hipFree(d_frame_pix_);
-  if (d_xidx_) (void)hipFree(d_xidx_);
-  if (d_acc_) (void)hipFree(d_acc_);
-  if (d_cnt_) (void)hipFree(d_cnt_);
-  if (d_rgba_) (void)hipFree(d_rgba_);
-  if (d_samp_) (void)hipFree(d_samp_);
-  if (d_work_) (void)hipFree(d_work_);
-  if (d_probe_) (void)hipFree(d_probe_);
-  if (d_fallback_) (void)hipFree(d_fallback_);
-  if (d_fh_) (void)hipFree(d_fh_);
-  if (d_fh_spill_) (void)hipFree(d_fh_spill_);
-  if (d_dn_) (void)hipFree(d_dn_);
+  free_partition();
+  free_frame();
   free_reproject();
-  free_guided();
+  d_work_.reset();
+  d_probe_.reset();
+  d_fallback_.reset();
+  d_fh_.reset();
+  d_fh_spill_.reset();
+  h_word_.reset();
   for (PathSet& L : lanes_) {
-    if (L.counts) (void)hipFree(L.counts);
-    if (L.h_counts) (void)hipHostFree(L.h_counts);
-    if (L.spill) (void)hipFree(L.spill);
-    if (L.done) (void)hipEventDestroy(L.done);
-    if (L.stream && L.stream != stream_) (void)hipStreamDestroy(L.stream);
-    if (L.lo) (void)hipStreamDestroy(L.lo);
+    L.counts.reset();
+    L.h_counts.reset();
+    L.spill.reset();
   }
-  for (int k = 0; k < 2; k++) {
-    if (d_seam_pix_[k]) (void)hipFree(d_seam_pix_[k]);
-    if (d_rest_pix_[k]) (void)hipFree(d_rest_pix_[k]);
-  }
-  if (h_fill_cnt_) (void)hipHostFree(h_fill_cnt_);
+  for (auto& re : refill_ev_)
+    for (hipEvent_t e : re)
+      if (e) (void)hipEventDestroy(e);
   for (auto& fe : fill_ev_)
     for (hipEvent_t e : fe)
       if (e) (void)hipEventDestroy(e);
+  for (PathSet& L : lanes_)
+    if (L.done) (void)hipEventDestroy(L.done);
   if (ev_main_) (void)hipEventDestroy(ev_main_);
   if (ev_sync_) (void)hipEventDestroy(ev_sync_);
   if (ev_ref_) (void)hipEventDestroy(ev_ref_);
-  if (h_word_) (void)hipHostFree(h_word_);
   for (auto& e : ev_pool_)
     if (e) (void)hipEventDestroy(e);
+  for (PathSet& L : lanes_) {
+    if (L.stream && L.stream != stream_) (void)hipStreamDestroy(L.stream);
+    if (L.lo) (void)hipStreamDestroy(L.lo);
+  }
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -2724,7 +2762,7 @@ bool Renderer::set_device(int dev, std::string& err) {
   HIP_OK(hipEventCreateWithFlags(&ev_main_, hipEventDisableTiming));
   HIP_OK(hipEventCreateWithFlags(&ev_sync_, hipEventDisableTiming));
   HIP_OK(hipEventCreate(&ev_ref_));
-  HIP_OK(hipHostMalloc(&h_word_, sizeof(uint32_t) * 4));
+  HIP_OK(h_word_.alloc(4));
   // every lane's stream is made here (a stream takes a hardware queue only
   // when it first submits work, so unused lanes cost nothing): the lane
   // count can then change per session, up to kMaxLanes
@@ -2734,33 +2772,36 @@ bool Renderer::set_device(int dev, std::string& err) {
     if (i == 0) L.stream = stream_;
     else HIP_OK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     HIP_OK(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
-    HIP_OK(hipMalloc(&L.counts, sizeof(uint32_t) * kCountWords));
-    HIP_OK(hipHostMalloc(&L.h_counts, sizeof(uint32_t) * kCountWords));
+    HIP_OK(L.counts.alloc(kCountWords));
+    HIP_OK(L.h_counts.alloc(kCountWords));
   }
-  HIP_OK(hipMalloc(&d_work_, sizeof(unsigned long long) * kWorkWords * kWorkCopies));
-  HIP_OK(hipMalloc(&d_fallback_, sizeof(uint32_t) * 4));  // [0..1] fallbacks, [2] stack overflow
+  HIP_OK(d_work_.alloc(kWorkWords * kWorkCopies));
+  HIP_OK(d_fallback_.alloc(4));  // [0..1] fallbacks, [2] stack overflow
   HIP_OK(hipMemset(d_fallback_, 0, sizeof(uint32_t) * 4));
   HIP_OK(hipMemset(d_work_, 0, sizeof(unsigned long long) * kWorkWords * kWorkCopies));
   return true;
 }
 
 void Renderer::free_scene() {
-  for (void* p : scene_bufs_) (void)hipFree(p);
   scene_bufs_.clear();
   scene_ok_ = false;
 }
 
 void Renderer::free_lane_paths(PathSet& L) {
-  void* bufs[] = {L.pixel, L.col, L.ro[0], L.rd[0], L.thr[0], L.ro[1], L.rd[1], L.thr[1], L.t, L.id, L.t1, L.id1,
-                  L.so, L.sd, L.sc};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  L.pixel = nullptr;
-  L.col = nullptr;
-  for (int k = 0; k < 2; k++) L.ro[k] = L.rd[k] = L.thr[k] = nullptr;
-  L.t = L.t1 = nullptr;
-  L.id = L.id1 = nullptr;
-  L.so = L.sd = L.sc = nullptr;
+  L.pixel.reset();
+  L.col.reset();
+  for (int k = 0; k < 2; k++) {
+    L.ro[k].reset();
+    L.rd[k].reset();
+    L.thr[k].reset();
+  }
+  L.t.reset();
+  L.id.reset();
+  L.t1.reset();
+  L.id1.reset();
+  L.so.reset();
+  L.sd.reset();
+  L.sc.reset();
   L.cap = 0;
 }
 
@@ -2837,9 +2878,9 @@ bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
     nodes[2 * i + 1] = make_float4(n.bmax[1], n.bmax[2], u2f(n.left_first), u2f(n.count));
   }
   auto up = [&](const void* src, size_t bytes, void** dst) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) { err = "hipMalloc failed (scene)"; return false; }
-    scene_bufs_.push_back(p);
+    scene_bufs_.emplace_back();
+    if (scene_bufs_.back().alloc(bytes) != hipSuccess) { err = "hipMalloc failed (scene)"; return false; }
+    void* p = scene_bufs_.back().get();
     if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy failed (scene)"; return false; }
     *dst = p;
     return true;
@@ -3042,7 +3083,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
       probe_cap_ = (uint32_t)v;
       probe_used_ = 0;
       probe_meta_.clear();
-      if (d_probe_) { (void)hipFree(d_probe_); d_probe_ = nullptr; }
+      d_probe_.reset();
       return true;
     default: err = "unknown option"; return false;
   }
@@ -3100,6 +3141,31 @@ bool Renderer::get_option(int opt, int64_t& v) const {
   }
 }
 
+// The viewport's frame and the scratch sized by it (the history and the merged
+// frame: free_reproject).
+void Renderer::free_frame() {
+  d_acc_.reset();
+  d_cnt_.reset();
+  d_rgba_.reset();
+  d_samp_.reset();
+  d_dn_.reset();
+}
+
+// The partition's pixel lists and what is sized by them.
+void Renderer::free_partition() {
+  d_part_pix_.reset();
+  d_frame_pix_.reset();
+  d_xidx_.reset();
+  for (int k = 0; k < 2; k++) {
+    d_half_pix_[k].reset();
+    d_seam_pix_[k].reset();
+    d_rest_pix_[k].reset();
+    half_npix_[k] = seam_npix_[k] = rest_npix_[k] = 0;
+  }
+  maxpart_ = 0;
+  free_guided();
+}
+
 bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
   if (!stream_) { err = "no device"; return false; }
   if (w == 0 || h == 0) { err = "empty viewport"; return false; }
@@ -3109,18 +3175,12 @@ bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
   w_ = w;
   h_ = h;
   free_rounds();
-  if (d_acc_) (void)hipFree(d_acc_);
-  if (d_cnt_) (void)hipFree(d_cnt_);
-  if (d_rgba_) (void)hipFree(d_rgba_);
-  if (d_samp_) (void)hipFree(d_samp_);
-  if (d_dn_) (void)hipFree(d_dn_);
-  d_acc_ = nullptr; d_cnt_ = nullptr; d_rgba_ = nullptr; d_samp_ = nullptr;
-  d_dn_ = nullptr; dn_cap_ = 0;
+  free_frame();
   free_reproject();
-  HIP_OK(hipMalloc(&d_acc_, sizeof(float4) * (size_t)w * h));
-  HIP_OK(hipMalloc(&d_cnt_, sizeof(uint32_t) * (size_t)w * h));
-  HIP_OK(hipMalloc(&d_rgba_, 4 * (size_t)w * h));
-  HIP_OK(hipMalloc(&d_samp_, 4 * (size_t)w * h));
+  HIP_OK(d_acc_.alloc((size_t)w * h));
+  HIP_OK(d_cnt_.alloc((size_t)w * h));
+  HIP_OK(d_rgba_.alloc(4 * (size_t)w * h));
+  HIP_OK(d_samp_.alloc(4 * (size_t)w * h));
   return set_partition(rank_, nranks_, tile_, err);
 }
 
@@ -3133,23 +3193,11 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
   HIP_OK(hipStreamSynchronize(stream_));  // and the main stream's (its frontier copy, a round's kernels)
   rank_ = rank; nranks_ = nranks; tile_ = tile;
   part_pix_.clear();
-  if (d_part_pix_) { (void)hipFree(d_part_pix_); d_part_pix_ = nullptr; }
-  for (uint32_t*& p : d_half_pix_)
-    if (p) { (void)hipFree(p); p = nullptr; }
-  for (int k = 0; k < 2; k++) {
-    if (d_seam_pix_[k]) { (void)hipFree(d_seam_pix_[k]); d_seam_pix_[k] = nullptr; }
-    if (d_rest_pix_[k]) { (void)hipFree(d_rest_pix_[k]); d_rest_pix_[k] = nullptr; }
-    seam_npix_[k] = rest_npix_[k] = 0;
-  }
-  if (d_frame_pix_) { (void)hipFree(d_frame_pix_); d_frame_pix_ = nullptr; }
-  half_npix_[0] = half_npix_[1] = 0;
-  if (d_xidx_) { (void)hipFree(d_xidx_); d_xidx_ = nullptr; }
-  maxpart_ = 0;
-  free_guided();
+  free_partition();
   if (w_ && h_ && nranks > 1) {
     tile_partition(w_, h_, rank, nranks, tile, part_pix_);
     if (!part_pix_.empty()) {
-      HIP_OK(hipMalloc(&d_part_pix_, sizeof(uint32_t) * part_pix_.size()));
+      HIP_OK(d_part_pix_.alloc(part_pix_.size()));
       HIP_OK(hipMemcpy(d_part_pix_, part_pix_.data(), sizeof(uint32_t) * part_pix_.size(), hipMemcpyHostToDevice));
     }
     // frame exchange index: entry j of rank r's gathered slot -> pixel
@@ -3162,7 +3210,7 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
     for (uint32_t r = 0; r < nranks; r++)
       std::copy(parts[r].begin(), parts[r].end(), xidx.begin() + (size_t)r * maxpart_);
     if (!xidx.empty()) {
-      HIP_OK(hipMalloc(&d_xidx_, sizeof(uint32_t) * xidx.size()));
+      HIP_OK(d_xidx_.alloc(xidx.size()));
       HIP_OK(hipMemcpy(d_xidx_, xidx.data(), sizeof(uint32_t) * xidx.size(), hipMemcpyHostToDevice));
     }
     // each screen half's own pixels as partition entries, in partition order
@@ -3174,7 +3222,7 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
         if ((part_pix_[i] % w_ >= half) == (hh == 1)) rows.push_back((uint32_t)i);
       half_npix_[hh] = (uint32_t)rows.size();
       if (!rows.empty()) {
-        HIP_OK(hipMalloc(&d_half_pix_[hh], sizeof(uint32_t) * rows.size()));
+        HIP_OK(d_half_pix_[hh].alloc(rows.size()));
         HIP_OK(hipMemcpy(d_half_pix_[hh], rows.data(), sizeof(uint32_t) * rows.size(), hipMemcpyHostToDevice));
       }
     }
@@ -3189,14 +3237,14 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
     const uint32_t tile_px = pixel_tile_;
     std::vector<uint32_t> px;
     tile_order(w_, h_, 0, w_, tile_px, px);
-    HIP_OK(hipMalloc(&d_frame_pix_, sizeof(uint32_t) * px.size()));
+    HIP_OK(d_frame_pix_.alloc(px.size()));
     HIP_OK(hipMemcpy(d_frame_pix_, px.data(), sizeof(uint32_t) * px.size(), hipMemcpyHostToDevice));
     const uint32_t half = w_ / 2;
     for (int hh = 0; hh < 2; hh++) {
       tile_order(w_, h_, hh ? half : 0u, hh ? w_ : half, tile_px, px);
       half_npix_[hh] = (uint32_t)px.size();
       if (!px.empty()) {
-        HIP_OK(hipMalloc(&d_half_pix_[hh], sizeof(uint32_t) * px.size()));
+        HIP_OK(d_half_pix_[hh].alloc(px.size()));
         HIP_OK(hipMemcpy(d_half_pix_[hh], px.data(), sizeof(uint32_t) * px.size(), hipMemcpyHostToDevice));
       }
       // the half's seam (the columns within the 5x5 error filter's radius 2
@@ -3210,11 +3258,11 @@ bool Renderer::set_partition(uint32_t rank, uint32_t nranks, uint32_t tile, std:
       seam_npix_[hh] = (uint32_t)seam.size();
       rest_npix_[hh] = (uint32_t)rest.size();
       if (!seam.empty()) {
-        HIP_OK(hipMalloc(&d_seam_pix_[hh], sizeof(uint32_t) * seam.size()));
+        HIP_OK(d_seam_pix_[hh].alloc(seam.size()));
         HIP_OK(hipMemcpy(d_seam_pix_[hh], seam.data(), sizeof(uint32_t) * seam.size(), hipMemcpyHostToDevice));
       }
       if (!rest.empty()) {
-        HIP_OK(hipMalloc(&d_rest_pix_[hh], sizeof(uint32_t) * rest.size()));
+        HIP_OK(d_rest_pix_[hh].alloc(rest.size()));
         HIP_OK(hipMemcpy(d_rest_pix_[hh], rest.data(), sizeof(uint32_t) * rest.size(), hipMemcpyHostToDevice));
       }
     }
@@ -3244,8 +3292,7 @@ bool Renderer::ensure_lane(int i, uint64_t n, std::string& err) {
   if (!L.spill) {
     // the lane's traversal-stack spill, for the largest persistent grid
     const size_t need = spill_slots() * (size_t)std::max<uint32_t>(max_grid(), 1) * kTBlock;
-    HIP_OK(hipMalloc(&L.spill, need * sizeof(uint2)));
-    L.spill_cap = need;
+    HIP_OK(L.spill.alloc(need));
   }
   if (async_prio_ && i >= kAsyncLane0 && !L.lo) {
     // async batches' low-priority stream (WPT_OPT_ASYNC_PRIO)
@@ -3258,18 +3305,18 @@ bool Renderer::ensure_lane(int i, uint64_t n, std::string& err) {
   if (L.lo) HIP_OK(hipStreamSynchronize(L.lo));
   HIP_OK(hipStreamSynchronize(stream_));
   free_lane_paths(L);
-  HIP_OK(hipMalloc(&L.pixel, 4 * n));
-  HIP_OK(hipMalloc(&L.col, 16 * n));
+  HIP_OK(L.pixel.alloc(n));
+  HIP_OK(L.col.alloc(n));
   for (int k = 0; k < 2; k++) {
-    HIP_OK(hipMalloc(&L.ro[k], 16 * n));
-    HIP_OK(hipMalloc(&L.rd[k], 16 * n));
-    HIP_OK(hipMalloc(&L.thr[k], 16 * n));
+    HIP_OK(L.ro[k].alloc(n));
+    HIP_OK(L.rd[k].alloc(n));
+    HIP_OK(L.thr[k].alloc(n));
   }
-  HIP_OK(hipMalloc(&L.t, 4 * n));
-  HIP_OK(hipMalloc(&L.id, 4 * n));
-  HIP_OK(hipMalloc(&L.so, 16 * n));
-  HIP_OK(hipMalloc(&L.sd, 16 * n));
-  HIP_OK(hipMalloc(&L.sc, 16 * n));
+  HIP_OK(L.t.alloc(n));
+  HIP_OK(L.id.alloc(n));
+  HIP_OK(L.so.alloc(n));
+  HIP_OK(L.sd.alloc(n));
+  HIP_OK(L.sc.alloc(n));
   L.cap = n;
   return true;
 }
@@ -3453,8 +3500,8 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
     if (B.presolve && !L.t1 && L.cap) {
       // the second pair of hit records, made with the lane's first presolving
       // batch: sessions that presolve nothing allocate what they did before
-      HIP_OK(hipMalloc(&L.t1, 4 * L.cap));
-      HIP_OK(hipMalloc(&L.id1, 4 * L.cap));
+      HIP_OK(L.t1.alloc(L.cap));
+      HIP_OK(L.id1.alloc(L.cap));
     }
     const LaunchCtx C = batch_ctx(B, i, 0);
     const hipStream_t s = C.stream;
@@ -3827,6 +3874,14 @@ LaunchCtx Renderer::lane0_ctx(bool count) const {
 // The ring for this rank's partition (pixels x slots radiance + ray counts,
 // and the refill id of each slot), the frontier (= the counts: an empty
 // ring), the round deficit and reduction scratch, the refill pool.
+void Renderer::free_stock_side() {
+  d_front_.reset();
+  d_def_.reset();
+  d_bmax_.reset();
+  d_rays_.reset();
+  for (Refill& f : refills_) f = Refill();
+}
+
 bool Renderer::stock_alloc(std::string& err) {
   const uint64_t np = part_pix_.size();
   // WPT_OPT_STOCK slots, fewer for large viewports: slot indices stay below
@@ -3841,35 +3896,26 @@ bool Renderer::stock_alloc(std::string& err) {
   HIP_OK(hipStreamSynchronize(stream_));
   ring_give(device_, d_stock_, stock_bytes_[0]);
   ring_give(device_, d_stock_id_, stock_bytes_[1]);
-  void* sb[] = {d_front_, d_def_, d_bmax_, d_rays_};
-  for (void* q : sb)
-    if (q) (void)hipFree(q);
   d_stock_ = nullptr;
-  d_stock_id_ = d_front_ = d_def_ = nullptr;
-  d_bmax_ = nullptr;
-  d_rays_ = nullptr;
+  d_stock_id_ = nullptr;
   stock_cap_ = 0;
-  for (Refill& f : refills_) {
-    if (f.off) (void)hipFree(f.off);
-    if (f.base) (void)hipFree(f.base);
-    f = Refill();
-  }
+  free_stock_side();
   const uint64_t nb = np / kBlock + 2;
   HIP_OK(ring_take(device_, sizeof(float4) * np * slots, (void**)&d_stock_, &stock_bytes_[0]));
   HIP_OK(ring_take(device_, sizeof(uint32_t) * np * slots, (void**)&d_stock_id_, &stock_bytes_[1]));
-  HIP_OK(hipMalloc(&d_front_, sizeof(uint32_t) * np));
-  HIP_OK(hipMalloc(&d_def_, sizeof(uint32_t) * (2 * np + 2)));
-  HIP_OK(hipMalloc(&d_bmax_, sizeof(uint32_t) * nb + 16));
-  HIP_OK(hipMalloc(&d_rays_, sizeof(unsigned long long) * (4 + 3 * nb)));
+  HIP_OK(d_front_.alloc(np));
+  HIP_OK(d_def_.alloc(2 * np + 2));
+  HIP_OK(d_bmax_.alloc(nb + 4));
+  HIP_OK(d_rays_.alloc(4 + 3 * nb));
   HIP_OK(hipMemsetAsync(d_rays_, 0, sizeof(unsigned long long) * 4, stream_));
   k_front_init<<<blocks_for(np), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, (uint32_t)np, d_cnt_, d_front_);
   HIP_OK(hipGetLastError());
   for (Refill& f : refills_) {
-    HIP_OK(hipMalloc(&f.off, sizeof(uint32_t) * (np + 1)));
-    HIP_OK(hipMalloc(&f.base, sizeof(uint32_t) * (np + 1)));
+    HIP_OK(f.off.alloc(np + 1));
+    HIP_OK(f.base.alloc(np + 1));
   }
   if (!h_refill_cnt_) {
-    HIP_OK(hipHostMalloc(&h_refill_cnt_, sizeof(uint32_t) * kMaxRefill * kRefillChunks * (kCountWords + 1)));
+    HIP_OK(h_refill_cnt_.alloc(kMaxRefill * kRefillChunks * (kCountWords + 1)));
     for (auto& re : refill_ev_)
       for (hipEvent_t& e : re) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
@@ -3930,13 +3976,7 @@ bool Renderer::stock_round(int h, uint64_t left, std::string& err) {
                                            global ? R.gbase : R.rbase, d_cnt_, d_front_, d_stock_id_, slots, def_cnt,
                                            def_base, bmax);
   k_max_reduce<<<1, 1024, 0, stream_>>>(bmax, nb, need);
-  auto scan = [&](uint32_t* a, uint32_t n) {
-    const uint32_t sb = (n + kScanChunk - 1) / kScanChunk;
-    k_scan_local<<<sb, kBlock, 0, stream_>>>(a, n, d_scan_sums_);
-    k_scan_sums<<<1, kBlock, 0, stream_>>>(d_scan_sums_, sb);
-    k_scan_add<<<sb, kBlock, 0, stream_>>>(a, n, d_scan_sums_);
-  };
-  scan(def_cnt, npix + 1);
+  scan_u32(stream_, def_cnt, npix + 1, d_scan_sums_);
   // the refill, sized by the positions of later rounds in this call
   Refill* F = nullptr;
   const uint64_t after = left > R.total ? left - R.total : 0;
@@ -4003,10 +4043,7 @@ void Renderer::refill_plan(Refill& F, int h, uint32_t ahead, uint32_t q) {
   k_refill_plan<<<blocks_for((uint64_t)nh + 1), kBlock, 0, stream_>>>(
       global ? d_part_pix_ : nullptr, d_half_pix_[h], nh, global ? rounds_[h].gc : rounds_[h].rc, d_cnt_, d_front_,
       d_stock_id_, stock_used_slots_, ahead, stock_extra_, q, refill_id_, F.off, F.base);
-  const uint32_t n = nh + 1, sb = (n + kScanChunk - 1) / kScanChunk;
-  k_scan_local<<<sb, kBlock, 0, stream_>>>(F.off, n, d_scan_sums_);
-  k_scan_sums<<<1, kBlock, 0, stream_>>>(d_scan_sums_, sb);
-  k_scan_add<<<sb, kBlock, 0, stream_>>>(F.off, n, d_scan_sums_);
+  scan_u32(stream_, F.off, nh + 1, d_scan_sums_);
 }
 
 // F's wt planned samples onto the next stock lane, in chunks its lane holds.
@@ -4023,7 +4060,7 @@ bool Renderer::refill_issue(Refill& F, int h, uint64_t wt, std::string& err) {
   }
   if (lanes_[l].cap < chunk && !drain_async(err)) return false;
   if (!ensure_lane(l, chunk, err)) return false;
-  if (async_oneshot_ && lanes_[l].spill_cap < spill_slots() * (size_t)oneshot_grid(chunk) * kTBlock &&
+  if (async_oneshot_ && lanes_[l].spill.cap() < spill_slots() * (size_t)oneshot_grid(chunk) * kTBlock &&
       (!drain_async(err) || !ensure_spill(l, oneshot_grid(chunk), err)))
     return false;
   F.id = refill_id_++;
@@ -4163,7 +4200,7 @@ bool Renderer::stock_flush(std::string& err) {
 // 2^25 paths; their counts land in stats_ at drain_fill.
 bool Renderer::issue_fill(int h, uint64_t k0, uint64_t n, std::string& err) {
   if (!h_fill_cnt_) {
-    HIP_OK(hipHostMalloc(&h_fill_cnt_, sizeof(uint32_t) * kMaxFill * (kCountWords + 1)));
+    HIP_OK(h_fill_cnt_.alloc(kMaxFill * (kCountWords + 1)));
     for (auto& fe : fill_ev_)
       for (hipEvent_t& e : fe) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
@@ -4171,7 +4208,7 @@ bool Renderer::issue_fill(int h, uint64_t k0, uint64_t n, std::string& err) {
   const int l = fill_lane();
   if (lanes_[l].cap < chunk && !drain_fill(err)) return false;
   if (!ensure_lane(l, chunk, err)) return false;
-  if (async_oneshot_ && lanes_[l].spill_cap < spill_slots() * (size_t)oneshot_grid(chunk) * kTBlock &&
+  if (async_oneshot_ && lanes_[l].spill.cap() < spill_slots() * (size_t)oneshot_grid(chunk) * kTBlock &&
       (!drain_fill(err) || !ensure_spill(l, oneshot_grid(chunk), err)))
     return false;
   for (uint64_t done = 0; done < n;) {
@@ -4514,15 +4551,8 @@ bool Renderer::results_rgba(uint8_t* out, std::string& err) {
 
 bool Renderer::read_radiance(float* acc3, uint32_t* cnt, std::string& err) {
   const size_t np = (size_t)w_ * h_;
-  std::vector<float4> a(np);
-  HIP_OK(hipMemcpyAsync(a.data(), d_acc_, sizeof(float4) * np, hipMemcpyDeviceToHost, stream_));
   if (cnt) HIP_OK(hipMemcpyAsync(cnt, d_cnt_, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < np; i++) {
-    acc3[3 * i] = a[i].x;
-    acc3[3 * i + 1] = a[i].y;
-    acc3[3 * i + 2] = a[i].z;
-  }
+  HIP_OK(download_rgb3(stream_, d_acc_, np, acc3));
   return true;
 }
 
@@ -4639,8 +4669,7 @@ uint4* Renderer::probe_slot(const LaunchCtx& C, int kernel, uint32_t grid) {
     // buffer stays below 4 GB
     const uint64_t cap_max = (1ull << 28) / std::max<uint32_t>(probe_waves_, 1);
     probe_cap_ = (uint32_t)std::min<uint64_t>(probe_cap_, cap_max);
-    if (hipMalloc(&d_probe_, sizeof(uint4) * (size_t)probe_waves_ * probe_cap_) != hipSuccess) {
-      d_probe_ = nullptr;
+    if (d_probe_.alloc((size_t)probe_waves_ * probe_cap_) != hipSuccess) {
       probe_cap_ = 0;
       return nullptr;
     }
@@ -4676,21 +4705,17 @@ size_t Renderer::spill_slots() const {
 // holds. Every launch is clamped to it (a smaller persistent grid loops over
 // more feed chunks, the same bits).
 uint32_t Renderer::spill_grid(const PathSet& L) const {
-  return (uint32_t)std::min<size_t>(L.spill_cap / (spill_slots() * kTBlock), 0xFFFFFFFFu);
+  return (uint32_t)std::min<size_t>(L.spill.cap() / (spill_slots() * kTBlock), 0xFFFFFFFFu);
 }
 
 // Lane l's spill area for grids of `grid` blocks (one-shot async grids).
 bool Renderer::ensure_spill(int l, uint32_t grid, std::string& err) {
   PathSet& L = lanes_[l];
   const size_t need = spill_slots() * (size_t)grid * kTBlock;
-  if (need <= L.spill_cap) return true;
+  if (need <= L.spill.cap()) return true;
   HIP_OK(hipStreamSynchronize(L.stream));
   if (L.lo) HIP_OK(hipStreamSynchronize(L.lo));
-  if (L.spill) (void)hipFree(L.spill);
-  L.spill = nullptr;
-  L.spill_cap = 0;
-  HIP_OK(hipMalloc(&L.spill, need * sizeof(uint2)));
-  L.spill_cap = need;
+  HIP_OK(L.spill.alloc(need));
   return true;
 }
 
@@ -4768,47 +4793,31 @@ bool Renderer::size_grids(std::string& err) {
   // for a deeper scene
   for (int i = 0; i < lanes_made_; i++) {
     PathSet& L = lanes_[i];
-    if (L.spill && need > L.spill_cap) {
+    if (L.spill && need > L.spill.cap()) {
       HIP_OK(hipStreamSynchronize(L.stream));
-      if (L.spill) (void)hipFree(L.spill);
-      L.spill = nullptr;
-      HIP_OK(hipMalloc(&L.spill, need * sizeof(uint2)));
-      L.spill_cap = need;
+      HIP_OK(L.spill.alloc(need));
     }
   }
   return true;
 }
 
 void Renderer::free_rounds() {
-  void* bufs[] = {d_scan_sums_, d_mse_[0], d_mse_[1], d_gsums_, d_bmm_};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  for (HalfRounds& r : rounds_) {
-    void* rb[] = {r.rc, r.rbase, r.gc, r.gbase};
-    for (void* p : rb)
-      if (p) (void)hipFree(p);
-    r = HalfRounds();
+  d_scan_sums_.reset();
+  d_gsums_.reset();
+  d_bmm_.reset();
+  for (int k = 0; k < 2; k++) {
+    d_mse_[k].reset();
+    h_mse_[k].reset();
+    rounds_[k] = HalfRounds();
   }
-  for (float*& h : h_mse_)
-    if (h) { (void)hipHostFree(h); h = nullptr; }
-  void* dbufs[] = {d_s64_, d_eff_, d_need_, d_list_, d_fb_};
-  for (void* p : dbufs)
-    if (p) (void)hipFree(p);
-  void* hbufs[] = {h_eff_, h_list_, h_fb_};
-  for (void* p : hbufs)
-    if (p) (void)hipHostFree(p);
-  d_s64_ = nullptr;
-  d_eff_ = nullptr;
-  d_need_ = nullptr;
-  d_list_ = nullptr;
-  d_fb_ = nullptr;
-  h_eff_ = nullptr;
-  h_list_ = nullptr;
-  h_fb_ = nullptr;
-  d_scan_sums_ = nullptr;
-  d_mse_[0] = d_mse_[1] = nullptr;
-  d_gsums_ = nullptr;
-  d_bmm_ = nullptr;
+  d_s64_.reset();
+  d_eff_.reset();
+  h_eff_.reset();
+  d_need_.reset();
+  d_list_.reset();
+  d_fb_.reset();
+  h_list_.reset();
+  h_fb_.reset();
   round_cap_ = 0;
 }
 
@@ -4925,11 +4934,7 @@ bool Renderer::plan_counts(uint32_t W, uint32_t H, uint32_t pn, int h, bool adap
   for (int k = 0; k < 3; k++) RP.stats[k] = stats[k];
   k_plan_round<<<blocks_for((uint64_t)pn + 1), kBlock, 0, stream_>>>(RP, nullptr, cnt_px, mse_l, mse_r, rc, rbase, samp);
   HIP_OK(hipGetLastError());
-  const uint32_t n = pn + 1;
-  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
-  k_scan_local<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
-  k_scan_sums<<<1, kBlock, 0, stream_>>>(sums, nb);
-  k_scan_add<<<nb, kBlock, 0, stream_>>>(rc, n, sums);
+  scan_u32(stream_, rc, pn + 1, sums);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(h_total, rc + pn, sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
   return host_wait_stream(stream_, err);
@@ -4947,39 +4952,38 @@ bool Renderer::plan_round(int h, std::string& err) {
   if (round_cap_ != (uint64_t)npix + 1 || (nranks_ > 1 && !rounds_[0].gc)) {
     // (re)allocate the round buffers; the halves' positions and round counts
     // stay (a non-adaptive half may have run whole rounds without a plan)
-    HalfRounds keep[2] = {rounds_[0], rounds_[1]};
+    const uint64_t total[2] = {rounds_[0].total, rounds_[1].total}, pos[2] = {rounds_[0].pos, rounds_[1].pos};
+    const uint32_t idx[2] = {rounds_[0].idx, rounds_[1].idx};
     free_rounds();
     for (int k = 0; k < 2; k++) {
-      rounds_[k].total = keep[k].total;
-      rounds_[k].pos = keep[k].pos;
-      rounds_[k].idx = keep[k].idx;
+      rounds_[k].total = total[k];
+      rounds_[k].pos = pos[k];
+      rounds_[k].idx = idx[k];
     }
     const RoundSizes Z = round_sizes(w_, h_, std::max(npix, np));
-    HIP_OK(hipMalloc(&d_scan_sums_, sizeof(uint32_t) * Z.scan_sums));
-    HIP_OK(hipMalloc(&d_mse_[0], sizeof(float) * Z.mse));
-    HIP_OK(hipMalloc(&d_mse_[1], sizeof(float) * Z.mse));
-    HIP_OK(hipMalloc(&d_bmm_, sizeof(uint32_t) * Z.bmm));
-    HIP_OK(hipHostMalloc(&h_mse_[0], sizeof(float) * Z.mse));
-    HIP_OK(hipHostMalloc(&h_mse_[1], sizeof(float) * Z.mse));
-    HIP_OK(hipMalloc(&d_s64_, sizeof(double) * Z.chunks));
-    HIP_OK(hipMalloc(&d_eff_, sizeof(ChunkEff) * 2 * Z.chunks));
-    HIP_OK(hipHostMalloc(&h_eff_, sizeof(ChunkEff) * 2 * Z.chunks));
-    HIP_OK(hipMalloc(&d_need_, sizeof(uint32_t) * Z.chunks));
-    HIP_OK(hipMalloc(&d_list_, sizeof(uint32_t) * (Z.chunks + 1)));
-    HIP_OK(hipMalloc(&d_fb_, sizeof(float) * Z.fetch));
-    HIP_OK(hipHostMalloc(&h_list_, sizeof(uint32_t) * (Z.chunks + 1)));
-    HIP_OK(hipHostMalloc(&h_fb_, sizeof(float) * Z.fetch));
+    HIP_OK(d_scan_sums_.alloc(Z.scan_sums));
+    HIP_OK(d_mse_[0].alloc(Z.mse));
+    HIP_OK(d_mse_[1].alloc(Z.mse));
+    HIP_OK(d_bmm_.alloc(Z.bmm));
+    HIP_OK(h_mse_[0].alloc(Z.mse));
+    HIP_OK(h_mse_[1].alloc(Z.mse));
+    HIP_OK(d_s64_.alloc(Z.chunks));
+    HIP_OK(d_eff_.alloc(2 * Z.chunks));
+    HIP_OK(h_eff_.alloc(2 * Z.chunks));
+    HIP_OK(d_need_.alloc(Z.chunks));
+    HIP_OK(d_list_.alloc(Z.chunks + 1));
+    HIP_OK(d_fb_.alloc(Z.fetch));
+    HIP_OK(h_list_.alloc(Z.chunks + 1));
+    HIP_OK(h_fb_.alloc(Z.fetch));
     for (HalfRounds& r : rounds_) {
-      HIP_OK(hipMalloc(&r.rc, sizeof(uint32_t) * (npix + 1)));
-      HIP_OK(hipMalloc(&r.rbase, sizeof(uint32_t) * (npix + 1)));
+      HIP_OK(r.rc.alloc((size_t)npix + 1));
+      HIP_OK(r.rbase.alloc((size_t)npix + 1));
       if (nranks_ > 1) {
-        HIP_OK(hipMalloc(&r.gc, sizeof(uint32_t) * (np + 1)));
-        HIP_OK(hipMalloc(&r.gbase, sizeof(uint32_t) * (np + 1)));
+        HIP_OK(r.gc.alloc((size_t)np + 1));
+        HIP_OK(r.gbase.alloc((size_t)np + 1));
       }
     }
-    if (nranks_ > 1) {
-      HIP_OK(hipMalloc(&d_gsums_, sizeof(uint32_t) * round_sizes(w_, h_, np).scan_sums));
-    }
+    if (nranks_ > 1) HIP_OK(d_gsums_.alloc(round_sizes(w_, h_, np).scan_sums));
     round_cap_ = (uint64_t)npix + 1;
   }
   HalfRounds& R = rounds_[h];
@@ -5012,70 +5016,33 @@ bool Renderer::seq_sum_device(const float* v, uint64_t n, float& out, std::strin
   const uint32_t cnt = (uint32_t)n, nch = (cnt + kSumChunk - 1) / kSumChunk;
   out = 0.0f;
   if (!cnt) return true;
-  float *dv = nullptr, *dfb = nullptr;
-  double* ds = nullptr;
-  ChunkEff* de = nullptr;
-  uint32_t *dn = nullptr, *dl = nullptr;
   std::vector<ChunkEff> he(2 * (size_t)nch);
   std::vector<uint32_t> hl(nch + 1);
   std::vector<float> hfb((size_t)kSumFetch * kSumChunk), scratch((size_t)nch * kSumChunk);
-  bool ok = hipMalloc(&dv, sizeof(float) * (size_t)nch * kSumChunk) == hipSuccess &&
-            hipMalloc(&ds, sizeof(double) * nch) == hipSuccess &&
-            hipMalloc(&de, sizeof(ChunkEff) * 2 * nch) == hipSuccess &&
-            hipMalloc(&dn, sizeof(uint32_t) * nch) == hipSuccess &&
-            hipMalloc(&dl, sizeof(uint32_t) * (nch + 1)) == hipSuccess &&
-            hipMalloc(&dfb, sizeof(float) * kSumFetch * kSumChunk) == hipSuccess;
-  if (ok) {
-    const uint32_t wb = (uint32_t)(((uint64_t)nch * 64u + kBlock - 1) / kBlock);
-    ok = hipMemcpyAsync(dv, v, sizeof(float) * cnt, hipMemcpyHostToDevice, stream_) == hipSuccess;
-    k_sum_chunks<<<wb, kBlock, 0, stream_>>>(dv, cnt, ds);
-    k_sum_scan<<<1, 256, 0, stream_>>>(ds, nch);
-    k_sum_eff<<<wb, kBlock, 0, stream_>>>(dv, cnt, ds, de, dn);
-    k_sum_pack<<<1, 1024, 0, stream_>>>(dv, cnt, nch, dn, dl, dfb);
-    ok = ok && hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(he.data(), de, sizeof(ChunkEff) * 2 * nch, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(hl.data(), dl, sizeof(uint32_t) * (nch + 1), hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(hfb.data(), dfb, sizeof(float) * hfb.size(), hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipStreamSynchronize(stream_) == hipSuccess;
-    if (ok) {
-      SumFetch F{hl.data(), hfb.data(), dv, scratch.data(), stream_, (size_t)cnt, 0u, true};
-      out = seq_sum_walk_fetch(cnt, he.data(), SumFetch::get, &F);
-      ok = F.ok;
-    }
-  }
-  void* bufs[] = {dv, dfb, ds, de, dn, dl};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  if (!ok) { err = "device sum failed"; return false; }
+  HookScratch S;
+  float* dv = S.d<float>((size_t)nch * kSumChunk);
+  double* ds = S.d<double>(nch);
+  ChunkEff* de = S.d<ChunkEff>(2 * (size_t)nch);
+  uint32_t* dn = S.d<uint32_t>(nch);
+  uint32_t* dl = S.d<uint32_t>((size_t)nch + 1);
+  float* dfb = S.d<float>((size_t)kSumFetch * kSumChunk);
+  if (!S.ok) { err = "hipMalloc failed (seq_sum_device)"; return false; }
+  const uint32_t wb = (uint32_t)(((uint64_t)nch * 64u + kBlock - 1) / kBlock);
+  HIP_OK(hipMemcpyAsync(dv, v, sizeof(float) * cnt, hipMemcpyHostToDevice, stream_));
+  k_sum_chunks<<<wb, kBlock, 0, stream_>>>(dv, cnt, ds);
+  k_sum_scan<<<1, 256, 0, stream_>>>(ds, nch);
+  k_sum_eff<<<wb, kBlock, 0, stream_>>>(dv, cnt, ds, de, dn);
+  k_sum_pack<<<1, 1024, 0, stream_>>>(dv, cnt, nch, dn, dl, dfb);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(he.data(), de, sizeof(ChunkEff) * 2 * nch, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(hl.data(), dl, sizeof(uint32_t) * (nch + 1), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(hfb.data(), dfb, sizeof(float) * hfb.size(), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  SumFetch F{hl.data(), hfb.data(), dv, scratch.data(), stream_, (size_t)cnt, 0u, true};
+  out = seq_sum_walk_fetch(cnt, he.data(), SumFetch::get, &F);
+  if (!F.ok) { err = "device sum failed"; return false; }
   return true;
 }
-
-// The wpt_adaptive_* hooks' buffers: device and pinned allocations freed
-// together.
-namespace {
-struct HookScratch {
-  std::vector<void*> dev, pinned;
-  bool ok = true;
-  template <class T>
-  T* d(size_t n) {
-    void* p = nullptr;
-    ok = ok && hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) == hipSuccess;
-    if (p) dev.push_back(p);
-    return (T*)p;
-  }
-  template <class T>
-  T* h(size_t n) {
-    void* p = nullptr;
-    ok = ok && hipHostMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) == hipSuccess;
-    if (p) pinned.push_back(p);
-    return (T*)p;
-  }
-  ~HookScratch() {
-    for (void* p : dev) (void)hipFree(p);
-    for (void* p : pinned) (void)hipHostFree(p);
-  }
-};
-}  // namespace
 
 bool Renderer::adaptive_error(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, int half, float* mse_out,
                               float* stats3, std::string& err) {
@@ -5091,9 +5058,8 @@ bool Renderer::adaptive_error(uint32_t W, uint32_t H, const float* acc3, const u
                     S.d<uint32_t>(Z.chunks),   S.d<uint32_t>(Z.chunks + 1), S.h<uint32_t>(Z.chunks + 1),
                     S.d<float>(Z.fetch),       S.h<float>(Z.fetch)};
   if (!S.ok) { err = "hipMalloc failed (adaptive_error)"; return false; }
-  std::vector<float4> a4(np);
-  for (uint32_t i = 0; i < np; i++) a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
-  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  std::vector<float4> a4;
+  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
   HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   if (!estimate_errors(d_acc, d_cnt, W, H, half, B, stats3, err)) return false;
@@ -5178,11 +5144,7 @@ bool Renderer::plan_slice(int h, uint64_t a, uint64_t b, uint64_t& local, std::s
   k_plan_slice<<<blocks_for((uint64_t)npix + 1), kBlock, 0, stream_>>>(d_part_pix_, npix, R.gc, R.gbase, (uint32_t)a,
                                                                       (uint32_t)b, R.rc, R.rbase);
   HIP_OK(hipGetLastError());
-  const uint32_t n = npix + 1;
-  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
-  k_scan_local<<<nb, kBlock, 0, stream_>>>(R.rc, n, d_scan_sums_);
-  k_scan_sums<<<1, kBlock, 0, stream_>>>(d_scan_sums_, nb);
-  k_scan_add<<<nb, kBlock, 0, stream_>>>(R.rc, n, d_scan_sums_);
+  scan_u32(stream_, R.rc, npix + 1, d_scan_sums_);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(h_word_, R.rc + npix, sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
@@ -5205,12 +5167,9 @@ bool Renderer::sampling_rgba(uint8_t* out, std::string& err) {
 }
 
 void Renderer::free_photons() {
-  if (d_oct_child_) (void)hipFree(d_oct_child_);
-  if (d_oct_cum_) (void)hipFree(d_oct_cum_);
-  if (d_oct_corners_) (void)hipFree(d_oct_corners_);
-  d_oct_child_ = nullptr;
-  d_oct_cum_ = nullptr;
-  d_oct_corners_ = nullptr;
+  d_oct_child_.reset();
+  d_oct_cum_.reset();
+  d_oct_corners_.reset();
   ds_.oct_child = nullptr;
   ds_.oct_cum = nullptr;
   ds_.oct_corners = nullptr;
@@ -5274,10 +5233,10 @@ bool Renderer::build_photons(std::string& err) {
 bool Renderer::upload_photons(const PhotonTree& tree, std::string& err) {
   photons_stored_ = tree.num_photons();
   tree.freeze(oct_child_, oct_cum_);
-  HIP_OK(hipMalloc(&d_oct_child_, sizeof(uint32_t) * oct_child_.size()));
+  HIP_OK(d_oct_child_.alloc(oct_child_.size()));
   HIP_OK(hipMemcpy(d_oct_child_, oct_child_.data(), sizeof(uint32_t) * oct_child_.size(), hipMemcpyHostToDevice));
   if (!oct_cum_.empty()) {
-    HIP_OK(hipMalloc(&d_oct_cum_, sizeof(float) * oct_cum_.size()));
+    HIP_OK(d_oct_cum_.alloc(oct_cum_.size()));
     HIP_OK(hipMemcpy(d_oct_cum_, oct_cum_.data(), sizeof(float) * oct_cum_.size(), hipMemcpyHostToDevice));
   }
   ds_.oct_child = d_oct_child_;
@@ -5286,7 +5245,7 @@ bool Renderer::upload_photons(const PhotonTree& tree, std::string& err) {
   {
     std::vector<uint32_t> corners;
     oct_corner_table(oct_child_, corners);
-    HIP_OK(hipMalloc(&d_oct_corners_, sizeof(uint32_t) * corners.size()));
+    HIP_OK(d_oct_corners_.alloc(corners.size()));
     HIP_OK(hipMemcpy(d_oct_corners_, corners.data(), sizeof(uint32_t) * corners.size(), hipMemcpyHostToDevice));
     ds_.oct_corners = d_oct_corners_;
   }
@@ -5334,36 +5293,26 @@ int Renderer::photon_sample(size_t n, const float* pts3, const uint32_t* states,
   else { err = "photon_sample: the tree does not fit this view"; return -1; }
   if (!table) S.oct_corners = nullptr;
   if (n == 0) return 1;
-  float* dp = nullptr;
-  uint32_t* ds = nullptr;
-  uint32_t* dl = nullptr;
-  float* df = nullptr;
-  uint32_t* dso = nullptr;
-  bool ok = hipMalloc(&dp, 12 * n) == hipSuccess && hipMalloc(&ds, 4 * n) == hipSuccess &&
-            hipMalloc(&dl, 4 * n) == hipSuccess && hipMalloc(&df, 4 * n) == hipSuccess &&
-            hipMalloc(&dso, 4 * n) == hipSuccess;
-  if (ok)
-    ok = hipMemcpyAsync(dp, pts3, 12 * n, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-         hipMemcpyAsync(ds, states, 4 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
-  if (ok) {
-    const uint32_t nn = (uint32_t)n, grid = (nn + kShadeBlock - 1) / kShadeBlock;
-    const size_t smem = 4 * (size_t)S.oct_lds_words;
-    if (view == 2) k_photon_sample<2><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
-    else if (view == 1) k_photon_sample<1><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
-    else k_photon_sample<0><<<grid, kShadeBlock, 0, stream_>>>(S, nn, dp, ds, dl, df, dso);
-    ok = hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(light, dl, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(pdf, df, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(states_out, dso, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipStreamSynchronize(stream_) == hipSuccess;
-  }
-  (void)hipFree(dp);
-  (void)hipFree(ds);
-  (void)hipFree(dl);
-  (void)hipFree(df);
-  (void)hipFree(dso);
-  if (!ok) err = "HIP error in photon_sample";
-  return ok ? 1 : 0;
+  HookScratch Z;
+  float* dp = Z.d<float>(3 * n);
+  uint32_t* ds = Z.d<uint32_t>(n);
+  uint32_t* dl = Z.d<uint32_t>(n);
+  float* df = Z.d<float>(n);
+  uint32_t* dso = Z.d<uint32_t>(n);
+  if (!Z.ok) { err = "hipMalloc failed (photon_sample)"; return 0; }
+  HIP_OK(hipMemcpyAsync(dp, pts3, 12 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(ds, states, 4 * n, hipMemcpyHostToDevice, stream_));
+  const uint32_t nn = (uint32_t)n, grid = (nn + kShadeBlock - 1) / kShadeBlock;
+  const size_t smem = 4 * (size_t)S.oct_lds_words;
+  if (view == 2) k_photon_sample<2><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
+  else if (view == 1) k_photon_sample<1><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
+  else k_photon_sample<0><<<grid, kShadeBlock, 0, stream_>>>(S, nn, dp, ds, dl, df, dso);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(light, dl, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(pdf, df, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(states_out, dso, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return 1;
 }
 
 bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id_out, std::string& err) {
@@ -5410,6 +5359,22 @@ bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, ui
   return true;
 }
 
+namespace {
+// first_hit's buffer for np pixels: the overflow flag, then the planes of
+// `mask`, each part 256 B aligned (a plane not wanted takes nothing)
+struct FhLayout {
+  size_t off[7] = {}, bytes = 0;
+  constexpr FhLayout(size_t np, uint32_t mask) {
+    Slices z;
+    z.take(sizeof(uint32_t));
+    for (int k = 0; k < 7; k++) off[k] = (mask >> k & 1u) ? z.take(kFhElem[k] * np) : z.at;
+    bytes = z.at;
+  }
+};
+static_assert(FhLayout(1000, 0x7Fu).bytes == 49664 && FhLayout(1000, 0x7Fu).off[6] == 48640, "first_hit's layout");
+static_assert(FhLayout(1000, 0x40u).bytes == 1280 && FhLayout(1000, 0x40u).off[6] == 256, "first_hit's layout");
+}  // namespace
+
 // k_first_hit of the planes in `mask` (bit k = plane k of wpt_first_hit's
 // order) into d_fh_, plane k at byte off[k]; returns once the kernel has ended
 // without a stack overflow.
@@ -5417,26 +5382,16 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   const size_t np = (size_t)w_ * h_;
-  // the flag, then the planes wanted, each 256 B aligned
-  size_t need = 256;
-  for (int k = 0; k < 7; k++) {
-    off[k] = need;
-    if (mask >> k & 1u) need += (kFhElem[k] * np + 255) / 256 * 256;
-  }
-  if (need > fh_cap_) {
-    if (d_fh_) (void)hipFree(d_fh_);
-    d_fh_ = nullptr;
-    fh_cap_ = 0;
-    HIP_OK(hipMalloc(&d_fh_, need));
-    fh_cap_ = need;
-  }
+  const FhLayout Z(np, mask);
+  std::copy(Z.off, Z.off + 7, off);
+  HIP_OK(d_fh_.grow(Z.bytes));
   FirstHitParams P;
   P.G = gen_params((uint32_t)np);
   P.sample = sample;
   P.mask = mask;
   P.tiles_x = (w_ + kFhTile - 1) / kFhTile;
   P.ntiles = P.tiles_x * ((h_ + kFhTile - 1) / kFhTile);
-  char* base = (char*)d_fh_;
+  char* base = d_fh_;
   P.dir = (float*)(base + off[0]);
   P.t = (float*)(base + off[1]);
   P.id = (int32_t*)(base + off[2]);
@@ -5450,16 +5405,10 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
   const size_t per_block = spill_slots() * kTBlock * sizeof(uint2);
   const uint32_t want = (P.ntiles + kTBlock / 64 - 1) / (kTBlock / 64);
   const uint32_t g = (uint32_t)std::max<size_t>(1, std::min<size_t>(want, kFhSpillBytes / per_block));
-  if ((size_t)g * per_block > fh_spill_cap_) {
-    if (d_fh_spill_) (void)hipFree(d_fh_spill_);
-    d_fh_spill_ = nullptr;
-    fh_spill_cap_ = 0;
-    HIP_OK(hipMalloc(&d_fh_spill_, (size_t)g * per_block));
-    fh_spill_cap_ = (size_t)g * per_block;
-  }
+  HIP_OK(d_fh_spill_.grow((size_t)g * per_block / sizeof(uint2)));
   DevScene ds = ds_;
   ds.probe = nullptr;
-  ds.overflow = (uint32_t*)d_fh_;
+  ds.overflow = (uint32_t*)d_fh_.get();
   HIP_OK(hipMemsetAsync(d_fh_, 0, sizeof(uint32_t), stream_));
   if (ds_.tri_only) k_first_hit<true><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
   else k_first_hit<false><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
@@ -5479,18 +5428,16 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
 // outputs rgb, rgba and valid; every part 256 B aligned.
 namespace {
 struct DnLayout {
-  size_t a0, a1, b, ap, rgb, rgba, valid, bytes;
-  explicit DnLayout(size_t np) {
-    size_t at = 0;
-    auto take = [&](size_t elem) {
-      const size_t o = at;
-      at += (elem * np + 255) / 256 * 256;
-      return o;
-    };
-    a0 = take(16); a1 = take(16); b = take(16); ap = take(12); rgb = take(12); rgba = take(4); valid = take(1);
-    bytes = at;
+  size_t a0 = 0, a1 = 0, b = 0, ap = 0, rgb = 0, rgba = 0, valid = 0, bytes = 0;
+  constexpr explicit DnLayout(size_t np) {
+    Slices z;
+    a0 = z.take(16 * np); a1 = z.take(16 * np); b = z.take(16 * np); ap = z.take(12 * np); rgb = z.take(12 * np);
+    rgba = z.take(4 * np); valid = z.take(np);
+    bytes = z.at;
   }
 };
+static_assert(DnLayout(1000).bytes == 77568 && DnLayout(1000).valid == 76544 && DnLayout(1000).ap == 48384,
+              "denoise's layout");
 
 template <int STEP>
 void launch_atrous(bool lds, dim3 grid, hipStream_t s, const float4* A, const float4* B, uint32_t W, uint32_t H,
@@ -5563,17 +5510,10 @@ bool Renderer::denoise(uint32_t sample, uint32_t iterations, float sigma_c, floa
   if (!rgb3 && !valid && !rgba) return true;
   size_t off[7];
   if (!first_hit_launch(sample, kFhT | kFhNormal | kFhAlbedo | kFhKind, off, err)) return false;
-  const size_t need = dn_bytes((size_t)w_ * h_);
-  if (need > dn_cap_) {
-    if (d_dn_) (void)hipFree(d_dn_);
-    d_dn_ = nullptr;
-    dn_cap_ = 0;
-    HIP_OK(hipMalloc(&d_dn_, need));
-    dn_cap_ = need;
-  }
-  const char* fh = (const char*)d_fh_;
+  HIP_OK(d_dn_.grow(dn_bytes((size_t)w_ * h_)));
+  const char* fh = d_fh_;
   return dn_run(w_, h_, d_acc_, d_cnt_, (const float*)(fh + off[1]), (const float*)(fh + off[4]),
-                (const float*)(fh + off[5]), (const uint8_t*)(fh + off[6]), (char*)d_dn_, iterations, sigma_c, sigma_z,
+                (const float*)(fh + off[5]), (const uint8_t*)(fh + off[6]), d_dn_, iterations, sigma_c, sigma_z,
                 flags, rgb3, valid, rgba, err);
 }
 
@@ -5593,9 +5533,8 @@ bool Renderer::denoise_planes(uint32_t W, uint32_t H, const float* acc3, const u
   uint8_t* d_kind = S.d<uint8_t>(np);
   char* scratch = S.d<char>(dn_bytes(np));
   if (!S.ok) { err = "hipMalloc failed (denoise_planes)"; return false; }
-  std::vector<float4> a4(np);
-  for (size_t i = 0; i < np; i++) a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
-  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  std::vector<float4> a4;
+  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
   HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_t, t, sizeof(float) * np, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
@@ -5613,20 +5552,11 @@ bool Renderer::denoise_planes(uint32_t W, uint32_t H, const float* acc3, const u
 namespace {
 // Parts of np pixels, each 256 B aligned: a kept frame's planes, and the merged
 // frame with the guide planes dn_run reads.
-struct RpSlices {
-  size_t at = 0, np;
-  explicit RpSlices(size_t n) : np(n) {}
-  size_t take(size_t elem) {
-    const size_t o = at;
-    at += (elem * np + 255) / 256 * 256;
-    return o;
-  }
-};
 struct RpHistLayout {
-  size_t k, r0, r1, id, bytes;
-  explicit RpHistLayout(size_t np) {
-    RpSlices z(np);
-    r0 = z.take(16); r1 = z.take(16); k = z.take(4); id = z.take(4);
+  size_t k = 0, r0 = 0, r1 = 0, id = 0, bytes = 0;
+  constexpr explicit RpHistLayout(size_t np) {
+    Slices z;
+    r0 = z.take(16 * np); r1 = z.take(16 * np); k = z.take(4 * np); id = z.take(4 * np);
     bytes = z.at;
   }
   RpHist at(void* base) const {
@@ -5636,25 +5566,27 @@ struct RpHistLayout {
     return h;
   }
 };
+static_assert(RpHistLayout(1000).bytes == 40448 && RpHistLayout(1000).k == 32256 && RpHistLayout(1000).id == 36352,
+              "the kept frame's layout");
 struct RpMergedLayout {
-  size_t acc, cnt, len, t, normal, albedo, kind, bytes;
-  explicit RpMergedLayout(size_t np) {
-    RpSlices z(np);
-    acc = z.take(16); cnt = z.take(4); len = z.take(4); t = z.take(4); normal = z.take(12); albedo = z.take(12);
-    kind = z.take(1);
+  size_t acc = 0, cnt = 0, len = 0, t = 0, normal = 0, albedo = 0, kind = 0, bytes = 0;
+  constexpr explicit RpMergedLayout(size_t np) {
+    Slices z;
+    acc = z.take(16 * np); cnt = z.take(4 * np); len = z.take(4 * np); t = z.take(4 * np); normal = z.take(12 * np);
+    albedo = z.take(12 * np); kind = z.take(np);
     bytes = z.at;
   }
 };
+static_assert(RpMergedLayout(1000).bytes == 53504 && RpMergedLayout(1000).len == 20224 &&
+                  RpMergedLayout(1000).kind == 52480,
+              "the merged frame's layout");
 const RpHist kNoHist = {nullptr, nullptr, nullptr, nullptr};
 }  // namespace
 
 void Renderer::free_reproject() {
-  for (void*& p : d_hist_) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-  if (d_rp_) (void)hipFree(d_rp_);
-  d_rp_ = nullptr;
+  d_hist_[0].reset();
+  d_hist_[1].reset();
+  d_rp_.reset();
   hist_cur_ = -1;
   rp_merged_ = false;
 }
@@ -5677,12 +5609,12 @@ bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t m
   const size_t np = (size_t)w_ * h_;
   const RpMergedLayout M(np);
   const RpHistLayout HL(np);
-  if (!d_rp_) HIP_OK(hipMalloc(&d_rp_, M.bytes));
+  HIP_OK(d_rp_.grow(M.bytes));
   const int into = hist_cur_ == 0 ? 1 : 0;  // the kept frame not being read
-  if (keep && !d_hist_[into]) HIP_OK(hipMalloc(&d_hist_[into], HL.bytes));
+  if (keep) HIP_OK(d_hist_[into].grow(HL.bytes));
   rp_merged_ = false;
-  const char* fh = (const char*)d_fh_;
-  char* m = (char*)d_rp_;
+  const char* fh = d_fh_;
+  char* m = d_rp_;
   RpParams P;
   P.A.W = w_; P.A.H = h_;
   P.A.cam = mk(cam_[0], cam_[1], cam_[2]);
@@ -5696,11 +5628,11 @@ bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t m
   P.id = need_id ? (const int32_t*)(fh + off[2]) : nullptr;
   P.normal = (const float*)(fh + off[4]);
   P.kind = (const uint8_t*)(fh + off[6]);
-  P.hist = hist_cur_ >= 0 ? HL.at(d_hist_[hist_cur_]) : kNoHist;
+  P.hist = hist_cur_ >= 0 ? HL.at(d_hist_[hist_cur_].get()) : kNoHist;
   P.acc_out = (float4*)(m + M.acc);
   P.cnt_out = (uint32_t*)(m + M.cnt);
   P.len_out = (uint32_t*)(m + M.len);
-  P.keep = keep ? HL.at(d_hist_[into]) : kNoHist;
+  P.keep = keep ? HL.at(d_hist_[into].get()) : kNoHist;
   hipStream_t s = lane0_ctx(false).stream;
   k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
   HIP_OK(hipGetLastError());
@@ -5709,16 +5641,9 @@ bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t m
   HIP_OK(hipMemcpyAsync(m + M.normal, fh + off[4], 12 * np, hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemcpyAsync(m + M.albedo, fh + off[5], 12 * np, hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemcpyAsync(m + M.kind, fh + off[6], np, hipMemcpyDeviceToDevice, s));
-  std::vector<float4> a4(acc3 ? np : 0);
-  if (acc3) HIP_OK(hipMemcpyAsync(a4.data(), P.acc_out, sizeof(float4) * np, hipMemcpyDeviceToHost, s));
   if (cnt) HIP_OK(hipMemcpyAsync(cnt, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
   if (len) HIP_OK(hipMemcpyAsync(len, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < a4.size(); i++) {
-    acc3[3 * i] = a4[i].x;
-    acc3[3 * i + 1] = a4[i].y;
-    acc3[3 * i + 2] = a4[i].z;
-  }
+  HIP_OK(download_rgb3(s, P.acc_out, np, acc3));
   rp_merged_ = true;
   rp_epoch_ = epoch_;
   if (keep) {
@@ -5734,18 +5659,11 @@ bool Renderer::denoise_merged(uint32_t iterations, float sigma_c, float sigma_z,
   if (!rp_merged_ || !d_rp_) { err = "no merged frame"; return false; }
   if (!rgb3 && !valid && !rgba) return true;
   const size_t np = (size_t)w_ * h_;
-  const size_t need = dn_bytes(np);
-  if (need > dn_cap_) {
-    if (d_dn_) (void)hipFree(d_dn_);
-    d_dn_ = nullptr;
-    dn_cap_ = 0;
-    HIP_OK(hipMalloc(&d_dn_, need));
-    dn_cap_ = need;
-  }
+  HIP_OK(d_dn_.grow(dn_bytes(np)));
   const RpMergedLayout M(np);
-  const char* m = (const char*)d_rp_;
+  const char* m = d_rp_;
   return dn_run(w_, h_, (const float4*)(m + M.acc), (const uint32_t*)(m + M.cnt), (const float*)(m + M.t),
-                (const float*)(m + M.normal), (const float*)(m + M.albedo), (const uint8_t*)(m + M.kind), (char*)d_dn_,
+                (const float*)(m + M.normal), (const float*)(m + M.albedo), (const uint8_t*)(m + M.kind), d_dn_,
                 iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err);
 }
 
@@ -5771,18 +5689,17 @@ bool Renderer::reproject_planes(uint32_t W, uint32_t H, const float* cam3, const
   uint8_t* d_kind = S.d<uint8_t>(np);
   char* d_h = S.d<char>(HL.bytes);
   if (!S.ok) { err = "hipMalloc failed (reproject_planes)"; return false; }
-  std::vector<float4> a4(np);
+  std::vector<float4> a4;
   std::vector<char> hb(HL.bytes, 0);
   const RpHist hh = HL.at(hb.data());
   for (size_t i = 0; i < np; i++) {
-    a4[i] = make_float4(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2], 0.0f);
     const RpKept k = rp_pack(mk(h_acc3[3 * i], h_acc3[3 * i + 1], h_acc3[3 * i + 2]), h_cnt[i]);
     hh.k[i] = (uint32_t)h_kind[i] | (k.valid ? 0x100u : 0u);
     hh.r0[i] = make_float4(k.c.x, k.c.y, k.c.z, u2f(h_cnt[i]));
     hh.r1[i] = make_float4(h_normal3[3 * i], h_normal3[3 * i + 1], h_normal3[3 * i + 2], h_t[i]);
     hh.id[i] = h_id[i];
   }
-  HIP_OK(hipMemcpyAsync(d_acc, a4.data(), sizeof(float4) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
   HIP_OK(hipMemcpyAsync(d_cnt, cnt, 4 * np, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_dir, dir3, 12 * np, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_t, t, 4 * np, hipMemcpyHostToDevice, stream_));
@@ -5804,16 +5721,9 @@ bool Renderer::reproject_planes(uint32_t W, uint32_t H, const float* cam3, const
   hipStream_t s = lane0_ctx(false).stream;
   k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
   HIP_OK(hipGetLastError());
-  if (acc3_out) HIP_OK(hipMemcpyAsync(a4.data(), P.acc_out, sizeof(float4) * np, hipMemcpyDeviceToHost, s));
   if (cnt_out) HIP_OK(hipMemcpyAsync(cnt_out, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
   if (len_out) HIP_OK(hipMemcpyAsync(len_out, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  if (acc3_out)
-    for (size_t i = 0; i < np; i++) {
-      acc3_out[3 * i] = a4[i].x;
-      acc3_out[3 * i + 1] = a4[i].y;
-      acc3_out[3 * i + 2] = a4[i].z;
-    }
+  HIP_OK(download_rgb3(s, P.acc_out, np, acc3_out));
   return true;
 }
 
@@ -5825,41 +5735,40 @@ namespace {
 // sample_map's scratch for np pixels: the needs and their scan (np + 1 u64),
 // the chunk sums, the map itself and the membership plane
 struct MapLayout {
-  size_t pre, sums, count, member, bytes;
-  uint32_t nb;
-  explicit MapLayout(size_t np) {
+  size_t pre = 0, sums = 0, count = 0, member = 0, bytes = 0;
+  uint32_t nb = 0;
+  constexpr explicit MapLayout(size_t np) {
     nb = (uint32_t)((np + 1 + kScanChunk - 1) / kScanChunk);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    pre = 0;
-    sums = pre + up(8 * (np + 1));
-    count = sums + up(8 * ((size_t)nb + 1));
-    member = count + up(4 * np);
-    bytes = member + up(np);
+    Slices z;
+    pre = z.take(8 * (np + 1)); sums = z.take(8 * ((size_t)nb + 1)); count = z.take(4 * np); member = z.take(np);
+    bytes = z.at;
   }
 };
 // compute_map's plan for a partition of npart of np pixels: the uploaded map,
 // the offsets (npart + 1) and bases, the scan's chunk sums, k_map_plan's words
 struct MapPlanLayout {
-  size_t in, off, base, sums, words, bytes;
-  uint32_t nb;
-  MapPlanLayout(size_t np, size_t npart) {
+  size_t in = 0, off = 0, base = 0, sums = 0, words = 0, bytes = 0;
+  uint32_t nb = 0;
+  constexpr MapPlanLayout(size_t np, size_t npart) {
     nb = (uint32_t)((npart + 1 + kScanChunk - 1) / kScanChunk);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    in = 0;
-    off = in + up(4 * np);
-    base = off + up(4 * (npart + 1));
-    sums = base + up(4 * npart);
-    words = sums + up(4 * ((size_t)nb + 1));
-    bytes = words + 256;
+    Slices z;
+    in = z.take(4 * np); off = z.take(4 * (npart + 1)); base = z.take(4 * npart); sums = z.take(4 * ((size_t)nb + 1));
+    words = z.take(256);
+    bytes = z.at;
   }
 };
+// (scans in chunks of 1024: 5000 pixels are 5 chunks)
+static_assert(kScanChunk == 1024 && MapLayout(5000).nb == 5 && MapLayout(5000).bytes == 65792 &&
+                  MapLayout(5000).count == 40448 && MapLayout(5000).member == 60672,
+              "sample_map's layout");
+static_assert(MapPlanLayout(5000, 2500).nb == 3 && MapPlanLayout(5000, 2500).bytes == 41216 &&
+                  MapPlanLayout(5000, 2500).sums == 40704 && MapPlanLayout(5000, 2500).words == 40960,
+              "compute_map's layout");
 }  // namespace
 
 void Renderer::free_guided() {
-  if (d_map_) (void)hipFree(d_map_);
-  if (d_mplan_) (void)hipFree(d_mplan_);
-  d_map_ = nullptr;
-  d_mplan_ = nullptr;
+  d_map_.reset();
+  d_mplan_.reset();
   map_ok_ = false;
 }
 
@@ -5910,12 +5819,12 @@ bool Renderer::sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uin
   if (flags & kMapMissOnce) {
     size_t off[7];
     if (!first_hit_launch(sample, kFhKind, off, err)) return false;
-    kind = (const uint8_t*)d_fh_ + off[6];
+    kind = (const uint8_t*)(d_fh_ + off[6]);
   }
   const MapLayout L(np);
-  if (!d_map_) HIP_OK(hipMalloc(&d_map_, L.bytes));
+  HIP_OK(d_map_.grow(L.bytes));
   map_ok_ = false;
-  char* m = (char*)d_map_;
+  char* m = d_map_;
   const uint8_t* member = nullptr;
   if (nranks_ > 1) {
     std::vector<uint8_t> mb(np, 0);
@@ -5925,7 +5834,7 @@ bool Renderer::sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uin
     member = (const uint8_t*)(m + L.member);
   }
   const uint32_t* len = nullptr;
-  if (rp_merged_ && d_rp_ && rp_epoch_ == epoch_) len = (const uint32_t*)((const char*)d_rp_ + RpMergedLayout(np).len);
+  if (rp_merged_ && d_rp_ && rp_epoch_ == epoch_) len = (const uint32_t*)(d_rp_ + RpMergedLayout(np).len);
   if (!map_run((uint32_t)np, d_cnt_, len, kind, member, m, target, max_pp, budget, flags, count_out, total_out, invalid,
                err))
     return false;
@@ -5978,15 +5887,15 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
   const size_t np = (size_t)w_ * h_;
   const uint32_t npart = (uint32_t)part_pix_.size();
   const MapPlanLayout L(np, npart);
-  if (!d_mplan_) HIP_OK(hipMalloc(&d_mplan_, L.bytes));
-  char* m = (char*)d_mplan_;
+  HIP_OK(d_mplan_.grow(L.bytes));
+  char* m = d_mplan_;
   uint32_t* off = (uint32_t*)(m + L.off);
   uint32_t* base = (uint32_t*)(m + L.base);
   uint32_t* sums = (uint32_t*)(m + L.sums);
   u64* words = (u64*)(m + L.words);
   const uint32_t* src = (const uint32_t*)(m + L.in);
   if (count) HIP_OK(hipMemcpyAsync(m + L.in, count, 4 * np, hipMemcpyHostToDevice, stream_));
-  else src = (const uint32_t*)((const char*)d_map_ + MapLayout(np).count);
+  else src = (const uint32_t*)(d_map_ + MapLayout(np).count);
   HIP_OK(hipMemsetAsync(words, 0, 2 * sizeof(u64), stream_));
   k_map_plan<<<blocks_for((uint64_t)npart + 1), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, npart, src,
                                                                      d_cnt_, off, base, words);
@@ -5998,10 +5907,7 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
   if (hw[0] > 0xFFFFFFFFull) { invalid = true; err = "compute_map: the map's counts sum to more than 2^32 - 1"; return false; }
   const uint64_t total = hw[0];
   if (total == 0) return true;
-  const uint32_t n = npart + 1;
-  k_scan_local<<<L.nb, kBlock, 0, stream_>>>(off, n, sums);
-  k_scan_sums<<<1, kBlock, 0, stream_>>>(sums, L.nb);
-  k_scan_add<<<L.nb, kBlock, 0, stream_>>>(off, n, sums);
+  scan_u32(stream_, off, npart + 1, sums);
   HIP_OK(hipGetLastError());
   const uint64_t bsz = std::min<uint64_t>(std::max<uint64_t>(batch_, 1), 0xFFFFFFFFull);
   if ((left_type_ == 2 || right_type_ == 2) && !build_photons(err)) return false;
@@ -6029,27 +5935,20 @@ bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, flo
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   if (n > 0xFFFFFFFFull / 8) { err = "too many rays"; return false; }
-  float* dr = nullptr;
-  float* dt = nullptr;
-  int32_t* di = nullptr;
-  uint8_t* df = nullptr;
-  bool ok = hipMalloc(&dr, 24 * n) == hipSuccess && hipMalloc(&dt, 4 * n) == hipSuccess &&
-            hipMalloc(&di, 4 * n) == hipSuccess && hipMalloc(&df, n) == hipSuccess;
-  if (ok) ok = hipMemcpyAsync(dr, rays, 24 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
-  if (ok) {
-    k_presolve<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dr, df, dt, di);
-    ok = hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(t_out, dt, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipMemcpyAsync(id_out, di, 4 * n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipStreamSynchronize(stream_) == hipSuccess;
-  }
-  (void)hipFree(dr);
-  (void)hipFree(dt);
-  (void)hipFree(di);
-  (void)hipFree(df);
-  if (!ok) err = "HIP error in presolve_rays";
-  return ok;
+  HookScratch S;
+  float* dr = S.d<float>(6 * n);
+  float* dt = S.d<float>(n);
+  int32_t* di = S.d<int32_t>(n);
+  uint8_t* df = S.d<uint8_t>(n);
+  if (!S.ok) { err = "hipMalloc failed (presolve_rays)"; return false; }
+  HIP_OK(hipMemcpyAsync(dr, rays, 24 * n, hipMemcpyHostToDevice, stream_));
+  k_presolve<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dr, df, dt, di);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(t_out, dt, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(id_out, di, 4 * n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return true;
 }
 
 bool Renderer::presolve_shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* resolved,
@@ -6057,38 +5956,23 @@ bool Renderer::presolve_shadow_rays(size_t n, const float* pq, const int32_t* li
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   if (n > 0xFFFFFFFFull / 16) { err = "too many rays"; return false; }
-  std::vector<float4> o(n), d(n);
-  for (size_t i = 0; i < n; i++) {
-    const float* r = pq + 6 * i;
-    V3 org, dir;
-    float dl;
-    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), org, dir, dl);
-    o[i] = make_float4(org.x, org.y, org.z, dl);
-    d[i] = make_float4(dir.x, dir.y, dir.z, u2f((uint32_t)light[i]));
-  }
-  float4* dso = nullptr;
-  float4* dsd = nullptr;
-  uint8_t* df = nullptr;
-  bool ok = hipMalloc(&dso, 16 * n) == hipSuccess && hipMalloc(&dsd, 16 * n) == hipSuccess &&
-            hipMalloc(&df, n) == hipSuccess;
-  if (ok)
-    ok = hipMemcpyAsync(dso, o.data(), 16 * n, hipMemcpyHostToDevice, stream_) == hipSuccess &&
-         hipMemcpyAsync(dsd, d.data(), 16 * n, hipMemcpyHostToDevice, stream_) == hipSuccess;
-  if (ok) {
-    k_presolve_shadow<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dso, dsd, df);
-    ok = hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
-         hipStreamSynchronize(stream_) == hipSuccess;
-  }
-  (void)hipFree(dso);
-  (void)hipFree(dsd);
-  (void)hipFree(df);
-  if (!ok) err = "HIP error in presolve_shadow_rays";
-  return ok;
+  std::vector<float4> o, d;
+  pack_shadow_rays(n, pq, light, o, d);
+  HookScratch S;
+  float4* dso = S.d<float4>(n);
+  float4* dsd = S.d<float4>(n);
+  uint8_t* df = S.d<uint8_t>(n);
+  if (!S.ok) { err = "hipMalloc failed (presolve_shadow_rays)"; return false; }
+  HIP_OK(hipMemcpyAsync(dso, o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(dsd, d.data(), 16 * n, hipMemcpyHostToDevice, stream_));
+  k_presolve_shadow<<<blocks_for((uint32_t)n), kBlock, 0, stream_>>>(ds_, (uint32_t)n, dso, dsd, df);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(resolved, df, n, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return true;
 }
 
-// Parity hook: the production shadow kernel on caller-given (p, q, light);
-// the shadow ray is formed as Scene::shadow_ray does (scene.rs:105-108).
+// Parity hook: the production shadow kernel on caller-given (p, q, light).
 bool Renderer::shadow_rays(size_t n, const float* pq, const int32_t* light, uint8_t* occ, std::string& err) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
@@ -6096,18 +5980,11 @@ bool Renderer::shadow_rays(size_t n, const float* pq, const int32_t* light, uint
   for (size_t i = 0; i < n; i++)
     if (light[i] < (int32_t)ds_.num_inf || light[i] >= (int32_t)ds_.num_shapes) { err = "light id out of range"; return false; }
   if (!ensure_paths(n, err)) return false;
-  std::vector<float4> o(n), d(n);
-  for (size_t i = 0; i < n; i++) {
-    const float* r = pq + 6 * i;
-    V3 org, dir;
-    float dl;
-    shadow_operands(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), org, dir, dl);
-    o[i] = make_float4(org.x, org.y, org.z, dl);
-    d[i] = make_float4(dir.x, dir.y, dir.z, u2f((uint32_t)light[i]));
-  }
-  uint8_t* dq = nullptr;
-  HIP_OK(hipMalloc(&dq, n));
-  const std::unique_ptr<uint8_t, void (*)(uint8_t*)> free_dq(dq, [](uint8_t* p) { (void)hipFree(p); });  // any return
+  std::vector<float4> o, d;
+  pack_shadow_rays(n, pq, light, o, d);
+  HookScratch S;
+  uint8_t* dq = S.d<uint8_t>(n);
+  if (!S.ok) { err = "hipMalloc failed (shadow_rays)"; return false; }
   const uint32_t nn = (uint32_t)n;
   const PathSet& L = lanes_[0];
   HIP_OK(hipMemcpyAsync(L.so, o.data(), 16 * n, hipMemcpyHostToDevice, stream_));
