@@ -574,6 +574,75 @@ int wpt_history_drop(void);
  * if no such call was made since the viewport was set. */
 int wpt_denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
                        uint8_t* rgba);
+/* wpt_first_hit's planes for the virtual viewport scale*width x scale*height
+ * (raster order, scale^2*width*height entries each) under the session's camera
+ * and frame seed: the ray of fine pixel (X, Y) is the one
+ * wpt_primary_rays(scale*width, scale*height, cam, seed, sample) gives; the
+ * aspect ratio and so the field of view are the session's. scale 1..4; scale 1
+ * is wpt_first_hit bit for bit. The planes are made in a buffer of their own:
+ * the guides wpt_denoise, wpt_reproject and wpt_sample_map work from are not
+ * disturbed, and the session is not touched, as with wpt_first_hit.
+ * WPT_ERR_INVALID_ARG: another scale, or scale^2*width*height >= 2^32. */
+int wpt_first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits,
+                         float* normal3, float* albedo3, uint8_t* kind);
+/* Guided upsampling of the session's W x H frame to sW x sH (joint bilateral
+ * upsampling with albedo demodulation): paths are traced at the session's
+ * viewport, the displayed frame takes its geometry (edges, emitters, albedo)
+ * from first-hit planes made at the fine viewport, wpt_first_hit_scaled(scale,
+ * sample)'s, on the device. The source is the session's frame as the calling
+ * rank holds it under the first-hit planes of `sample`, or with
+ * WPT_UPSAMPLE_MERGED the merged frame and guide planes the last successful
+ * wpt_reproject left on the device (what wpt_denoise_merged reads; the same
+ * error when there is none).
+ *  Coarse stage: wpt_denoise's pack with WPT_DENOISE_ALBEDO always on (diffuse
+ *  pixels hold irradiance = mean / albedo), then `iterations` (0..5; 0: none)
+ *  of its passes, WPT_OPT_DENOISE_LDS choosing the kernels as there.
+ *  Fine pixel (X, Y) of kind K (the fine planes'):
+ *   K = 0  the scene's background, valid 1.   K = 2  the emitter's intensity
+ *   (the fine albedo plane), valid 1: exact for every render type, the
+ *   reference adds throughput (1,1,1) * intensity at a first hit and returns.
+ *   K = 1  a = 2X + 1 - s, x0 = floor(a / 2s), fx = (a - 2s x0) / 2s, likewise
+ *   y; the coarse pixels (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with
+ *   the bilinear weights of (fx, fy). A tap outside the coarse viewport, not
+ *   diffuse, without samples or without a finite value is never read. Weight
+ *   w = bilinear * max(N . n_q, 0)^32 * 1 / (1 + r^2), r = |T - t_q| / (sigma_z
+ *   * T), with the fine pixel's normal N and depth T; taps with w > 0 are
+ *   averaged and the fine pixel's albedo (a component of 0 reads as 1) is
+ *   multiplied back: valid 1. If no tap passes, the 4 x 4 coarse block
+ *   x0-1..x0+2, y0-1..y0+2 under the same tests with bilinear = 1: valid 2.
+ *   If none passes there either: +0, valid 0.
+ * The definition to the operation: DESIGN.md §2; every output bit is that of
+ * wpt_upsample_host on the same planes while |acc / cnt| <= 2^100. Emitters and
+ * misses need no such bound; a coarse pixel without samples or with a
+ * non-finite value is never read; nothing crosses a kind edge or a normal edge
+ * with dot 0.
+ *  rgb3   3 f32  sW x sH     valid  u8  0, 1, 2 as above
+ *  rgba   4 u8   (clamp(rgb, 0, 1) * 255) as u8, alpha 255
+ * Any output may be NULL; with all of them NULL nothing is launched. The
+ * session, the history and the sample map are only read (wpt_stats and
+ * wpt_kernel_times too are unchanged).
+ * WPT_ERR_INVALID_ARG: scale outside 2..4, iterations above 5, a sigma not
+ * finite or <= 0, an unknown flag (MERGED is one to the two functions below),
+ * scale^2*W*H >= 2^32; for the two functions below also a null input or W*H == 0. */
+#define WPT_UPSAMPLE_MERGED 1u       /* session call only */
+int wpt_upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                 float* rgb3, uint8_t* valid, uint8_t* rgba);
+/* Test hook: the same kernels and launch geometry on a caller's planes, in
+ * buffers of its own: the coarse W x H frame and guides (as wpt_denoise_planes
+ * takes them), the fine sW x sH guides (as wpt_first_hit_scaled gives them)
+ * and the background's 3 f32. Needs wpt_init. */
+int wpt_upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
+                        const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
+                        const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
+                        const float* background3, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                        float* rgb3, uint8_t* valid, uint8_t* rgba);
+/* Host only (no session, no GPU): the restatement, the same functions the
+ * kernels call. */
+int wpt_upsample_host(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
+                      const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
+                      const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
+                      const float* background3, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                      float* rgb3, uint8_t* valid, uint8_t* rgba);
 /* Test hook: the same kernel and launch geometry on a caller's W x H planes, in
  * buffers of its own, no state kept. cam3: the current camera's position; acc3,
  * cnt as wpt_read_radiance gives them; dir3, t, id, normal3, kind as

@@ -71,6 +71,10 @@ _SIGS = {
     "wpt_reproject": (ctypes.c_int, [c_u32, c_f32, c_f32, c_u32, c_u32, c_p, c_p, c_p]),
     "wpt_history_drop": (ctypes.c_int, []),
     "wpt_denoise_merged": (ctypes.c_int, [c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
+    "wpt_first_hit_scaled": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "wpt_upsample": (ctypes.c_int, [c_u32, c_u32, c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
+    "wpt_upsample_planes": (ctypes.c_int, [c_u32, c_u32, c_u32] + [c_p] * 11 + [c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
+    "wpt_upsample_host": (ctypes.c_int, [c_u32, c_u32, c_u32] + [c_p] * 11 + [c_u32, c_f32, c_f32, c_u32, c_p, c_p, c_p]),
     "wpt_reproject_planes": (ctypes.c_int, [c_u32, c_u32] + [c_p] * 15 + [c_f32, c_f32, c_u32, c_u32, c_p, c_p, c_p]),
     "wpt_reproject_host": (ctypes.c_int, [c_u32, c_u32] + [c_p] * 15 + [c_f32, c_f32, c_u32, c_u32, c_p, c_p, c_p]),
     "wpt_sample_map": (ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),

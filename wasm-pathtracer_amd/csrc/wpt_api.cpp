@@ -27,6 +27,7 @@ namespace {
 #include "wpt_denoise.h"    // the host part: the restatement wpt_denoise_host runs
 #include "wpt_reproject.h"  // likewise wpt_reproject_host's
 #include "wpt_guided.h"     // and wpt_sample_map_host's
+#include "wpt_upsample.h"   // and wpt_upsample_host's
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -809,6 +810,26 @@ int wpt_first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t*
   return WPT_OK;
 }
 
+namespace {
+// scale^2 * W * H >= 2^32: a fine pixel's index would not fit 32 bits
+bool scaled_too_large(uint32_t W, uint32_t H, uint32_t scale) {
+  const uint64_t np = (uint64_t)W * H;
+  return np >= (1ull << 32) || np * scale * scale >= (1ull << 32);
+}
+}  // namespace
+
+int wpt_first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits,
+                         float* normal3, float* albedo3, uint8_t* kind) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (scale == 0 || scale > kUpMaxScale) return fail(WPT_ERR_INVALID_ARG, "first_hit_scaled: scale 1..4");
+  if (scaled_too_large(g_session->renderer.width(), g_session->renderer.height(), scale))
+    return fail(WPT_ERR_INVALID_ARG, "first_hit_scaled: the scaled viewport has 2^32 pixels or more");
+  std::string err;
+  if (!g_session->renderer.first_hit_scaled(scale, sample, dir3, t, id, visits, normal3, albedo3, kind, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 // gen_path's ray on the host: the same primary_dir (wpt_math.h) over the
 // constants Renderer::gen_params makes.
 int wpt_primary_rays(uint32_t width, uint32_t height, const float* cam5, uint32_t frame_seed, uint32_t sample,
@@ -923,6 +944,73 @@ int wpt_denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32
   std::string err;
   if (!g_session->renderer.denoise_merged(iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err))
     return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+namespace {
+// the argument rules the upsampling entry points share; MERGED is the session call's alone
+const char* upsample_args(uint32_t scale, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                          uint32_t known) {
+  if (scale < 2 || scale > kUpMaxScale) return "upsample: scale 2..4";
+  if (iterations > kDnMaxIter) return "upsample: iterations 0..5";
+  if (!dn_finite(sigma_c) || !(sigma_c > 0.0f) || !dn_finite(sigma_z) || !(sigma_z > 0.0f))
+    return "upsample: sigmas must be finite and > 0";
+  if (flags & ~known) return "upsample: unknown flag";
+  return nullptr;
+}
+const char* upsample_plane_args(uint32_t W, uint32_t H, uint32_t scale, std::initializer_list<const void*> in) {
+  for (const void* p : in)
+    if (!p) return "null pointer";
+  if ((uint64_t)W * H == 0 || scaled_too_large(W, H, scale)) return "bad frame size";
+  return nullptr;
+}
+}  // namespace
+
+int wpt_upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                 float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = upsample_args(scale, iterations, sigma_c, sigma_z, flags, WPT_UPSAMPLE_MERGED))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  if (scaled_too_large(g_session->renderer.width(), g_session->renderer.height(), scale))
+    return fail(WPT_ERR_INVALID_ARG, "upsample: the scaled viewport has 2^32 pixels or more");
+  if ((flags & WPT_UPSAMPLE_MERGED) && !g_session->renderer.has_merged())
+    return fail(WPT_ERR_INVALID_ARG, "upsample: no wpt_reproject since the viewport was set");
+  std::string err;
+  if (!g_session->renderer.upsample(scale, sample, iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
+                        const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
+                        const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
+                        const float* background3, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                        float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = upsample_args(scale, iterations, sigma_c, sigma_z, flags, 0u)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = upsample_plane_args(W, H, scale, {acc3, cnt, t, normal3, albedo3, kind, hi_t, hi_normal3,
+                                                         hi_albedo3, hi_kind, background3}))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.upsample_planes(W, H, scale, acc3, cnt, t, normal3, albedo3, kind, hi_t, hi_normal3,
+                                           hi_albedo3, hi_kind, background3, iterations, sigma_c, sigma_z, rgb3, valid,
+                                           rgba, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_upsample_host(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
+                      const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
+                      const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
+                      const float* background3, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                      float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  if (const char* e = upsample_args(scale, iterations, sigma_c, sigma_z, flags, 0u)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = upsample_plane_args(W, H, scale, {acc3, cnt, t, normal3, albedo3, kind, hi_t, hi_normal3,
+                                                         hi_albedo3, hi_kind, background3}))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  if (!rgb3 && !valid && !rgba) return WPT_OK;
+  upsample_host(W, H, scale, acc3, cnt, t, normal3, albedo3, kind, hi_t, hi_normal3, hi_albedo3, hi_kind, background3,
+                iterations, sigma_c, sigma_z, rgb3, valid, rgba);
   return WPT_OK;
 }
 

@@ -108,13 +108,24 @@ WPT_HD void dn_add(DnTapSum& s, float w, V3 cq) {
   s.sw = s.sw + w;
 }
 
-// The restatement on the host: the same functions, pixel by pixel.
-inline void denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
-                         const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
-                         float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba) {
+// The restatement on the host: the same functions, pixel by pixel. Its first
+// half, the pack and the passes (iterations may be 0), is also the coarse stage
+// of upsample_host (wpt_upsample.h): c the filtered value, ap = a', ok = valid.
+struct DnHostFrame {
+  std::vector<V3> c, ap;
+  std::vector<uint8_t> ok;
+};
+inline void dn_host_passes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                           const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                           float sigma_c, float sigma_z, uint32_t flags, DnHostFrame& F) {
   const size_t np = (size_t)W * H;
-  std::vector<V3> c0(np), c1(np), ap(np);
-  std::vector<uint8_t> ok(np);
+  std::vector<V3> c1(np);
+  std::vector<V3>& c0 = F.c;
+  std::vector<V3>& ap = F.ap;
+  std::vector<uint8_t>& ok = F.ok;
+  c0.resize(np);
+  ap.resize(np);
+  ok.resize(np);
   for (size_t i = 0; i < np; i++) {
     const DnPix p = dn_pack(mk(acc3[3 * i], acc3[3 * i + 1], acc3[3 * i + 2]), cnt[i],
                             mk(albedo3[3 * i], albedo3[3 * i + 1], albedo3[3 * i + 2]), kind[i], flags);
@@ -153,6 +164,17 @@ inline void denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32
     c0.swap(c1);
     sig = sig * 0.5f;
   }
+}
+
+inline void denoise_host(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
+                         const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
+                         float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba) {
+  DnHostFrame F;
+  dn_host_passes(W, H, acc3, cnt, t, normal3, albedo3, kind, iterations, sigma_c, sigma_z, flags, F);
+  const std::vector<V3>& c0 = F.c;
+  const std::vector<V3>& ap = F.ap;
+  const std::vector<uint8_t>& ok = F.ok;
+  const size_t np = (size_t)W * H;
   for (size_t i = 0; i < np; i++) {
     const V3 o = mk(c0[i].x * ap[i].x, c0[i].y * ap[i].y, c0[i].z * ap[i].z);
     if (rgb3) { rgb3[3 * i] = o.x; rgb3[3 * i + 1] = o.y; rgb3[3 * i + 2] = o.z; }

@@ -317,6 +317,25 @@ class Renderer {
   // (wpt_first_hit, include/wpt.h); a null plane is not computed
   bool first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
                  float* albedo3, uint8_t* kind, std::string& err);
+  // the same planes for the virtual viewport scale * width x scale * height
+  // under the session's camera and seed (wpt_first_hit_scaled), in a buffer of
+  // its own: first_hit's, which the filter, the reprojection and the sample map
+  // leave their guides in, is not written. The caller checks scale.
+  bool first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits,
+                        float* normal3, float* albedo3, uint8_t* kind, std::string& err);
+  // guided upsampling (wpt_upsample.h) of the session's frame, or with
+  // kUpMerged of the last reproject's merged frame (the caller checks
+  // has_merged()), to scale times the viewport: the filter's pack and passes at
+  // the session viewport, then k_upsample under the fine first-hit planes of
+  // `sample`; a null output is not written
+  bool upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
+                float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
+  // test hook: the same kernels and launch geometry on a caller's planes
+  bool upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
+                       const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
+                       const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
+                       const float* background3, uint32_t iterations, float sigma_c, float sigma_z, float* rgb3,
+                       uint8_t* valid, uint8_t* rgba, std::string& err);
   // the a-trous filter (wpt_denoise.h) on the session's frame, guided by the
   // first-hit planes of `sample` (wpt_denoise); a null output is not written
   bool denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
@@ -434,7 +453,8 @@ class Renderer {
   // the Batch state machine: lanes and generate; bounces until done or a
   // live-count read is pending (block: wait for it); the tail
   auto shade_params() const;  // the ShadeParams of a batch's shade kernels (wpt_render.hip)
-  auto gen_params(uint32_t npix) const;  // the GenParams of a mapping over npix entries (wpt_render.hip)
+  // the GenParams of a mapping over npix entries, for the viewport scale * w_ x scale * h_ (wpt_render.hip)
+  auto gen_params(uint32_t npix, uint32_t scale = 1) const;
   bool batch_begin(Batch& B, std::string& err);
   bool batch_advance(Batch& B, bool block, std::string& err);
   bool batch_tail(Batch& B, std::string& err);
@@ -711,8 +731,13 @@ class Renderer {
   // planes; the traversal-stack spill area of its grid
   DevBuf<char> d_fh_;
   DevBuf<uint2> d_fh_spill_;
-  // k_first_hit of the planes in `mask` into d_fh_ (plane k at off[k]); waits for it
-  bool first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err);
+  // k_first_hit of the planes in `mask` into d_fh_ (plane k at off[k]); waits
+  // for it. scale != 0: the virtual viewport scale * w_ x scale * h_, into d_fhs_.
+  bool first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err, uint32_t scale = 0);
+  // the scaled planes' buffer (first_hit_scaled, upsample's fine guides) and
+  // upsample's outputs; made on first use, freed with the viewport
+  DevBuf<char> d_fhs_;
+  DevBuf<char> d_up_;
   // denoise's scratch for the session's viewport (records A0, A1, B, a' and
   // the outputs), made on first use, freed with the viewport; the filter
   // itself over device planes in a scratch of dn_bytes(W * H)
@@ -721,6 +746,18 @@ class Renderer {
   bool dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
               const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
               float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
+  // dn_run's first half, which upsample shares: pack and the passes, queued on
+  // lane 0's stream; the result is record plane `cur` (0: A0, 1: A1) beside B and a'
+  bool dn_passes(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
+                 const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
+                 float sigma_z, uint32_t flags, int& cur, std::string& err);
+  // k_upsample over the records dn_passes left in dn_scratch (plane cur) and
+  // fine device planes, outputs in up_scratch (up_bytes(fine pixels)), copied
+  // to the host and waited for
+  static size_t up_bytes(size_t nf);
+  bool up_run(uint32_t W, uint32_t H, uint32_t scale, const char* dn_scratch, int cur, const float* hi_t,
+              const float* hi_normal, const float* hi_albedo, const uint8_t* hi_kind, const float bg[3], float sigma_z,
+              char* up_scratch, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
   uint32_t dn_lds_ = 7;  // WPT_OPT_DENOISE_LDS
   // Reprojection. epoch_ counts the resets of the accumulation (reset() is the
   // one place each passes through); a history kept at the current epoch already

@@ -2607,6 +2607,8 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 #include "wpt_reproject.h"
 #define WPT_GUIDED_KERNELS
 #include "wpt_guided.h"
+#define WPT_UPSAMPLE_KERNELS
+#include "wpt_upsample.h"
 
 }  // namespace
 
@@ -3149,6 +3151,8 @@ void Renderer::free_frame() {
   d_rgba_.reset();
   d_samp_.reset();
   d_dn_.reset();
+  d_fhs_.reset();
+  d_up_.reset();
 }
 
 // The partition's pixel lists and what is sized by them.
@@ -3454,17 +3458,19 @@ auto Renderer::shade_params() const {
 }
 
 // The frame, camera, seed and render types as the generate kernels take them,
-// for a mapping over npix entries.
-auto Renderer::gen_params(uint32_t npix) const {
+// for a mapping over npix entries; scale > 1: over the virtual viewport
+// scale * w_ x scale * h_ (first_hit_launch; the camera and seed stay).
+auto Renderer::gen_params(uint32_t npix, uint32_t scale) const {
+  const uint32_t vw = scale * w_, vh = scale * h_;
   GenParams G;
-  G.W = w_; G.H = h_; G.npix = npix;
-  const View v = make_view(w_, h_, cam_[3], cam_[4]);
+  G.W = vw; G.H = vh; G.npix = npix;
+  const View v = make_view(vw, vh, cam_[3], cam_[4]);
   G.w_inv = v.w_inv; G.h_inv = v.h_inv; G.ar = v.ar;
   G.cam[0] = cam_[0]; G.cam[1] = cam_[1]; G.cam[2] = cam_[2];
   G.cx = v.cx; G.sx = v.sx;
   G.cy = v.cy; G.sy = v.sy;
   G.seed = seed_;
-  G.half = w_ / 2;
+  G.half = vw / 2;
   G.left_type = (uint32_t)left_type_; G.right_type = (uint32_t)right_type_;
   return G;
 }
@@ -5359,6 +5365,23 @@ bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, ui
   return true;
 }
 
+bool Renderer::first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id,
+                                uint32_t* visits, float* normal3, float* albedo3, uint8_t* kind, std::string& err) {
+  const uint32_t mask = (dir3 ? kFhDir : 0u) | (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) |
+                        (normal3 ? kFhNormal : 0u) | (albedo3 ? kFhAlbedo : 0u) | (kind ? kFhKind : 0u);
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
+  if (mask == 0) return true;
+  size_t off[7];
+  if (!first_hit_launch(sample, mask, off, err, scale)) return false;
+  const size_t np = (size_t)scale * w_ * ((size_t)scale * h_);
+  void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
+  for (int k = 0; k < 7; k++)
+    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], (char*)d_fhs_ + off[k], kFhElem[k] * np, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  return true;
+}
+
 namespace {
 // first_hit's buffer for np pixels: the overflow flag, then the planes of
 // `mask`, each part 256 B aligned (a plane not wanted takes nothing)
@@ -5377,21 +5400,25 @@ static_assert(FhLayout(1000, 0x40u).bytes == 1280 && FhLayout(1000, 0x40u).off[6
 
 // k_first_hit of the planes in `mask` (bit k = plane k of wpt_first_hit's
 // order) into d_fh_, plane k at byte off[k]; returns once the kernel has ended
-// without a stack overflow.
-bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err) {
+// without a stack overflow. scale != 0: the planes of the virtual viewport
+// scale * w_ x scale * h_ (the camera, the seed and so the field of view are the
+// session's; the caller checks that it has fewer than 2^32 pixels), into d_fhs_.
+bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err, uint32_t scale) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
-  const size_t np = (size_t)w_ * h_;
+  const uint32_t vw = scale ? scale * w_ : w_, vh = scale ? scale * h_ : h_;
+  DevBuf<char>& buf = scale ? d_fhs_ : d_fh_;
+  const size_t np = (size_t)vw * vh;
   const FhLayout Z(np, mask);
   std::copy(Z.off, Z.off + 7, off);
-  HIP_OK(d_fh_.grow(Z.bytes));
+  HIP_OK(buf.grow(Z.bytes));
   FirstHitParams P;
-  P.G = gen_params((uint32_t)np);
+  P.G = gen_params((uint32_t)np, scale ? scale : 1u);
   P.sample = sample;
   P.mask = mask;
-  P.tiles_x = (w_ + kFhTile - 1) / kFhTile;
-  P.ntiles = P.tiles_x * ((h_ + kFhTile - 1) / kFhTile);
-  char* base = d_fh_;
+  P.tiles_x = (vw + kFhTile - 1) / kFhTile;
+  P.ntiles = P.tiles_x * ((vh + kFhTile - 1) / kFhTile);
+  char* base = buf;
   P.dir = (float*)(base + off[0]);
   P.t = (float*)(base + off[1]);
   P.id = (int32_t*)(base + off[2]);
@@ -5408,13 +5435,13 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
   HIP_OK(d_fh_spill_.grow((size_t)g * per_block / sizeof(uint2)));
   DevScene ds = ds_;
   ds.probe = nullptr;
-  ds.overflow = (uint32_t*)d_fh_.get();
-  HIP_OK(hipMemsetAsync(d_fh_, 0, sizeof(uint32_t), stream_));
+  ds.overflow = (uint32_t*)buf.get();
+  HIP_OK(hipMemsetAsync(buf, 0, sizeof(uint32_t), stream_));
   if (ds_.tri_only) k_first_hit<true><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
   else k_first_hit<false><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
   HIP_OK(hipGetLastError());
   uint32_t flag = 0;
-  HIP_OK(hipMemcpyAsync(&flag, d_fh_, sizeof flag, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(&flag, buf, sizeof flag, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   if (flag) { err = "traversal stack overflow (results invalid)"; return false; }
   return true;
@@ -5454,29 +5481,25 @@ void launch_atrous(bool lds, dim3 grid, hipStream_t s, const float4* A, const fl
 
 size_t Renderer::dn_bytes(size_t np) { return DnLayout(np).bytes; }
 
-// Pack, the iterations and unpack over device planes, on lane 0's stream,
-// neither timed nor counted; the outputs wanted are copied to the host and
-// waited for. Iteration i runs the LDS kernel if bit i of WPT_OPT_DENOISE_LDS
-// is set (steps 1, 2, 4 only), else the direct one.
-bool Renderer::dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
-                      const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
-                      uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
-                      uint8_t* rgba, std::string& err) {
-  const LaunchCtx C = lane0_ctx(false);
-  hipStream_t s = C.stream;
+// Pack and the iterations over device planes, queued on lane 0's stream,
+// neither timed nor counted; the filtered records are plane `cur` of the
+// scratch. Iteration i runs the LDS kernel if bit i of WPT_OPT_DENOISE_LDS is
+// set (steps 1, 2, 4 only), else the direct one.
+bool Renderer::dn_passes(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
+                         const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
+                         uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, int& cur,
+                         std::string& err) {
+  hipStream_t s = lane0_ctx(false).stream;
   const size_t np = (size_t)W * H;
   const DnLayout Z(np);
   float4* A[2] = {(float4*)(scratch + Z.a0), (float4*)(scratch + Z.a1)};
   float4* B = (float4*)(scratch + Z.b);
   float* ap = (float*)(scratch + Z.ap);
-  float* d_rgb = rgb3 ? (float*)(scratch + Z.rgb) : nullptr;
-  uint8_t* d_rgba = rgba ? (uint8_t*)(scratch + Z.rgba) : nullptr;
-  uint8_t* d_valid = valid ? (uint8_t*)(scratch + Z.valid) : nullptr;
   k_dn_pack<<<blocks_for(np), kBlock, 0, s>>>(acc, cnt, t, normal, albedo, kind, (uint32_t)np, flags, A[0], B, ap);
   HIP_OK(hipGetLastError());
   const dim3 grid((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile);
   float sig = sigma_c;
-  int cur = 0;
+  cur = 0;
   for (uint32_t i = 0; i < iterations; i++) {
     const float s2 = sig * sig;
     const bool lds = (dn_lds_ >> i & 1u) != 0;
@@ -5491,7 +5514,28 @@ bool Renderer::dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t*
     cur ^= 1;
     sig = sig * 0.5f;
   }
-  k_dn_unpack<<<blocks_for(np), kBlock, 0, s>>>(A[cur], B, ap, (uint32_t)np, d_rgb, d_valid, d_rgba);
+  return true;
+}
+
+// The filter over device planes: dn_passes, then unpack; the outputs wanted
+// are copied to the host and waited for.
+bool Renderer::dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
+                      const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
+                      uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
+                      uint8_t* rgba, std::string& err) {
+  int cur = 0;
+  if (!dn_passes(W, H, acc, cnt, t, normal, albedo, kind, scratch, iterations, sigma_c, sigma_z, flags, cur, err))
+    return false;
+  hipStream_t s = lane0_ctx(false).stream;
+  const size_t np = (size_t)W * H;
+  const DnLayout Z(np);
+  const float4* A = (const float4*)(scratch + (cur ? Z.a1 : Z.a0));
+  const float4* B = (const float4*)(scratch + Z.b);
+  const float* ap = (const float*)(scratch + Z.ap);
+  float* d_rgb = rgb3 ? (float*)(scratch + Z.rgb) : nullptr;
+  uint8_t* d_rgba = rgba ? (uint8_t*)(scratch + Z.rgba) : nullptr;
+  uint8_t* d_valid = valid ? (uint8_t*)(scratch + Z.valid) : nullptr;
+  k_dn_unpack<<<blocks_for(np), kBlock, 0, s>>>(A, B, ap, (uint32_t)np, d_rgb, d_valid, d_rgba);
   HIP_OK(hipGetLastError());
   if (rgb3) HIP_OK(hipMemcpyAsync(rgb3, d_rgb, 12 * np, hipMemcpyDeviceToHost, s));
   if (valid) HIP_OK(hipMemcpyAsync(valid, d_valid, np, hipMemcpyDeviceToHost, s));
@@ -5665,6 +5709,135 @@ bool Renderer::denoise_merged(uint32_t iterations, float sigma_c, float sigma_z,
   return dn_run(w_, h_, (const float4*)(m + M.acc), (const uint32_t*)(m + M.cnt), (const float*)(m + M.t),
                 (const float*)(m + M.normal), (const float*)(m + M.albedo), (const uint8_t*)(m + M.kind), d_dn_,
                 iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err);
+}
+
+// ---------------------------------------------------------------------------
+// Guided upsampling (wpt_upsample.h)
+// ---------------------------------------------------------------------------
+
+namespace {
+// The outputs of a fine frame of nf pixels; every part 256 B aligned.
+struct UpLayout {
+  size_t rgb = 0, rgba = 0, valid = 0, bytes = 0;
+  constexpr explicit UpLayout(size_t nf) {
+    Slices z;
+    rgb = z.take(12 * nf); rgba = z.take(4 * nf); valid = z.take(nf);
+    bytes = z.at;
+  }
+};
+static_assert(UpLayout(1000).bytes == 17152 && UpLayout(1000).rgba == 12032 && UpLayout(1000).valid == 16128,
+              "upsample's layout");
+}  // namespace
+
+size_t Renderer::up_bytes(size_t nf) { return UpLayout(nf).bytes; }
+
+// k_upsample on lane 0's stream after the passes dn_passes queued there,
+// neither timed nor counted.
+bool Renderer::up_run(uint32_t W, uint32_t H, uint32_t scale, const char* dn_scratch, int cur, const float* hi_t,
+                      const float* hi_normal, const float* hi_albedo, const uint8_t* hi_kind, const float bg[3],
+                      float sigma_z, char* up_scratch, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
+  hipStream_t s = lane0_ctx(false).stream;
+  const DnLayout Z((size_t)W * H);
+  UpParams P;
+  P.A.W = W; P.A.H = H; P.A.s = scale;
+  P.A.sigma_z = sigma_z;
+  P.A.bg = mk(bg[0], bg[1], bg[2]);
+  P.fw = scale * W; P.fh = scale * H;
+  const size_t nf = (size_t)P.fw * P.fh;
+  const UpLayout U(nf);
+  P.rec.A = (const float4*)(dn_scratch + (cur ? Z.a1 : Z.a0));
+  P.rec.B = (const float4*)(dn_scratch + Z.b);
+  P.t = hi_t; P.normal = hi_normal; P.albedo = hi_albedo; P.kind = hi_kind;
+  P.rgb = rgb3 ? (float*)(up_scratch + U.rgb) : nullptr;
+  P.rgba = rgba ? (uint8_t*)(up_scratch + U.rgba) : nullptr;
+  P.valid = valid ? (uint8_t*)(up_scratch + U.valid) : nullptr;
+  const dim3 grid((P.fw + kDnTile - 1) / kDnTile, (P.fh + kDnTile - 1) / kDnTile);
+  k_upsample<<<grid, kBlock, 0, s>>>(P);
+  HIP_OK(hipGetLastError());
+  if (rgb3) HIP_OK(hipMemcpyAsync(rgb3, P.rgb, 12 * nf, hipMemcpyDeviceToHost, s));
+  if (valid) HIP_OK(hipMemcpyAsync(valid, P.valid, nf, hipMemcpyDeviceToHost, s));
+  if (rgba) HIP_OK(hipMemcpyAsync(rgba, P.rgba, 4 * nf, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return true;
+}
+
+// The session's frame as this rank holds it under k_first_hit's planes of
+// `sample`, or (kUpMerged) the merged frame and guides the last reproject left
+// in d_rp_; the fine guides are the scaled planes of `sample`. Everything stays
+// on the device; the frame, the counts, the rounds, the stock, the history, the
+// sample map and the counters are only read.
+bool Renderer::upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z,
+                        uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
+  const bool merged = (flags & kUpMerged) != 0;
+  if (merged && (!rp_merged_ || !d_rp_)) { err = "no merged frame"; return false; }
+  if (!rgb3 && !valid && !rgba) return true;
+  constexpr uint32_t kGuides = kFhT | kFhNormal | kFhAlbedo | kFhKind;
+  const size_t np = (size_t)w_ * h_, nf = (size_t)scale * w_ * ((size_t)scale * h_);
+  size_t off[7], hoff[7];
+  if (!merged && !first_hit_launch(sample, kGuides, off, err)) return false;
+  if (!first_hit_launch(sample, kGuides, hoff, err, scale)) return false;
+  HIP_OK(d_dn_.grow(dn_bytes(np)));
+  HIP_OK(d_up_.grow(up_bytes(nf)));
+  const RpMergedLayout M(np);
+  const char* fh = d_fh_;
+  const char* m = d_rp_;
+  const float4* acc = merged ? (const float4*)(m + M.acc) : d_acc_.get();
+  const uint32_t* cnt = merged ? (const uint32_t*)(m + M.cnt) : d_cnt_.get();
+  const float* t = (const float*)(merged ? m + M.t : fh + off[1]);
+  const float* normal = (const float*)(merged ? m + M.normal : fh + off[4]);
+  const float* albedo = (const float*)(merged ? m + M.albedo : fh + off[5]);
+  const uint8_t* kind = (const uint8_t*)(merged ? m + M.kind : fh + off[6]);
+  int cur = 0;
+  if (!dn_passes(w_, h_, acc, cnt, t, normal, albedo, kind, d_dn_, iterations, sigma_c, sigma_z, kDnAlbedo, cur, err))
+    return false;
+  const char* hi = d_fhs_;
+  return up_run(w_, h_, scale, d_dn_, cur, (const float*)(hi + hoff[1]), (const float*)(hi + hoff[4]),
+                (const float*)(hi + hoff[5]), (const uint8_t*)(hi + hoff[6]), ds_.bg, sigma_z, d_up_, rgb3, valid, rgba,
+                err);
+}
+
+bool Renderer::upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt,
+                               const float* t, const float* normal3, const float* albedo3, const uint8_t* kind,
+                               const float* hi_t, const float* hi_normal3, const float* hi_albedo3,
+                               const uint8_t* hi_kind, const float* background3, uint32_t iterations, float sigma_c,
+                               float sigma_z, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
+  if (!stream_) { err = "no device"; return false; }
+  if (!rgb3 && !valid && !rgba) return true;
+  const size_t np = (size_t)W * H, nf = (size_t)scale * W * ((size_t)scale * H);
+  HookScratch S;
+  float4* d_acc = S.d<float4>(np);
+  uint32_t* d_cnt = S.d<uint32_t>(np);
+  float* d_t = S.d<float>(np);
+  float* d_n = S.d<float>(3 * np);
+  float* d_al = S.d<float>(3 * np);
+  uint8_t* d_kind = S.d<uint8_t>(np);
+  float* d_ht = S.d<float>(nf);
+  float* d_hn = S.d<float>(3 * nf);
+  float* d_hal = S.d<float>(3 * nf);
+  uint8_t* d_hkind = S.d<uint8_t>(nf);
+  char* dn_scratch = S.d<char>(dn_bytes(np));
+  char* up_scratch = S.d<char>(up_bytes(nf));
+  if (!S.ok) { err = "hipMalloc failed (upsample_planes)"; return false; }
+  std::vector<float4> a4;
+  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
+  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_t, t, sizeof(float) * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_al, albedo3, 12 * np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_ht, hi_t, sizeof(float) * nf, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_hn, hi_normal3, 12 * nf, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_hal, hi_albedo3, 12 * nf, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipMemcpyAsync(d_hkind, hi_kind, nf, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  int cur = 0;
+  if (!dn_passes(W, H, d_acc, d_cnt, d_t, d_n, d_al, d_kind, dn_scratch, iterations, sigma_c, sigma_z, kDnAlbedo, cur,
+                 err))
+    return false;
+  return up_run(W, H, scale, dn_scratch, cur, d_ht, d_hn, d_hal, d_hkind, background3, sigma_z, up_scratch, rgb3, valid,
+                rgba, err);
 }
 
 // The history's planes are packed on the host with rp_pack, the function a

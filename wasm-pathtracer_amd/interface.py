@@ -599,6 +599,83 @@ def reproject_host(cam, cur, prev_cam, hist, cos_min=REPROJECT_DEFAULTS["cos_min
     return _reproject_planes(lib().wpt_reproject_host, cam, cur, prev_cam, hist, cos_min, eps_z, max_len, flags)
 
 
+def first_hit_scaled(scale, sample=0, planes=("dir", "t", "id", "visits", "normal", "albedo", "kind")):
+    """first_hit()'s planes for the virtual viewport scale * W x scale * H under
+    the session's camera and seed (wpt_first_hit_scaled): a dict plane name ->
+    (scale * H, scale * W) or (scale * H, scale * W, 3) array. scale 1..4."""
+    vp = get_option("viewport")
+    w, h = scale * (vp & 0xFFFFFFFF), scale * (vp >> 32)
+    out, ptr = {}, [None] * 7
+    for name in planes:
+        pos, dt, c = FIRST_HIT_PLANES[name]
+        out[name] = np.empty((h, w, 3) if c == 3 else (h, w), dtype=dt)
+        ptr[pos] = out[name].ctypes.data
+    _check(lib().wpt_first_hit_scaled(scale, sample, *ptr))
+    return out
+
+
+UPSAMPLE_MERGED = 1  # WPT_UPSAMPLE_MERGED: the source is the last reproject()'s merged frame and guides
+# the documented defaults of upsample(): the filter's sigmas and passes (profiles/upsample/README.md)
+UPSAMPLE_DEFAULTS = {"scale": 2, "iterations": DENOISE_DEFAULTS["iterations"], "sigma_c": DENOISE_DEFAULTS["sigma_c"],
+                     "sigma_z": DENOISE_DEFAULTS["sigma_z"], "flags": 0}
+
+
+def upsample(scale=UPSAMPLE_DEFAULTS["scale"], sample=0, iterations=UPSAMPLE_DEFAULTS["iterations"],
+             sigma_c=UPSAMPLE_DEFAULTS["sigma_c"], sigma_z=UPSAMPLE_DEFAULTS["sigma_z"],
+             flags=UPSAMPLE_DEFAULTS["flags"]):
+    """The session's W x H frame upsampled to scale * W x scale * H under
+    first-hit planes made at the fine viewport (wpt_upsample): (rgb (sH, sW, 3)
+    f32, valid (sH, sW) u8: 0 nothing passed, 1 exact or the four taps, 2 the
+    4 x 4 block, rgba (sH, sW, 4) u8). iterations 0..5 of the filter run on the
+    coarse irradiance first. With UPSAMPLE_MERGED the source is the last
+    reproject()'s merged frame. The session is not touched."""
+    vp = get_option("viewport")
+    rgb, valid, rgba = _denoise_out(scale * (vp & 0xFFFFFFFF), scale * (vp >> 32))
+    _check(lib().wpt_upsample(scale, sample, iterations, sigma_c, sigma_z, flags, rgb.ctypes.data, valid.ctypes.data,
+                              rgba.ctypes.data))
+    return rgb, valid, rgba
+
+
+def _upsample_planes(fn, scale, coarse, fine, background, iterations, sigma_c, sigma_z, flags):
+    acc, cnt, t, normal, albedo, kind = coarse
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    h, w = cnt.shape
+    fh, fw = scale * h, scale * w
+    acc = np.ascontiguousarray(acc, dtype=np.float32).reshape(h, w, 3)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(h, w)
+    normal = np.ascontiguousarray(normal, dtype=np.float32).reshape(h, w, 3)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32).reshape(h, w, 3)
+    kind = np.ascontiguousarray(kind, dtype=np.uint8).reshape(h, w)
+    ht, hn, ha, hk = fine
+    ht = np.ascontiguousarray(ht, dtype=np.float32).reshape(fh, fw)
+    hn = np.ascontiguousarray(hn, dtype=np.float32).reshape(fh, fw, 3)
+    ha = np.ascontiguousarray(ha, dtype=np.float32).reshape(fh, fw, 3)
+    hk = np.ascontiguousarray(hk, dtype=np.uint8).reshape(fh, fw)
+    bg = np.ascontiguousarray(background, dtype=np.float32).reshape(3)
+    rgb, valid, rgba = _denoise_out(fw, fh)
+    _check(fn(w, h, scale, acc.ctypes.data, cnt.ctypes.data, t.ctypes.data, normal.ctypes.data, albedo.ctypes.data,
+              kind.ctypes.data, ht.ctypes.data, hn.ctypes.data, ha.ctypes.data, hk.ctypes.data, bg.ctypes.data,
+              iterations, sigma_c, sigma_z, flags, rgb.ctypes.data, valid.ctypes.data, rgba.ctypes.data))
+    return rgb, valid, rgba
+
+
+def upsample_planes(scale, coarse, fine, background=(0.0, 0.0, 0.0), iterations=UPSAMPLE_DEFAULTS["iterations"],
+                    sigma_c=UPSAMPLE_DEFAULTS["sigma_c"], sigma_z=UPSAMPLE_DEFAULTS["sigma_z"], flags=0):
+    """Test hook (wpt_upsample_planes): upsample()'s kernels on the caller's
+    planes. coarse = (acc, cnt, t, normal, albedo, kind) at (H, W), cnt sizing
+    the frame; fine = (t, normal, albedo, kind) at (scale * H, scale * W).
+    Needs init."""
+    return _upsample_planes(lib().wpt_upsample_planes, scale, coarse, fine, background, iterations, sigma_c, sigma_z,
+                            flags)
+
+
+def upsample_host(scale, coarse, fine, background=(0.0, 0.0, 0.0), iterations=UPSAMPLE_DEFAULTS["iterations"],
+                  sigma_c=UPSAMPLE_DEFAULTS["sigma_c"], sigma_z=UPSAMPLE_DEFAULTS["sigma_z"], flags=0):
+    """The upsampler's host restatement (wpt_upsample_host): no session, no GPU."""
+    return _upsample_planes(lib().wpt_upsample_host, scale, coarse, fine, background, iterations, sigma_c, sigma_z,
+                            flags)
+
+
 MAP_MISS_ONCE = 1  # WPT_MAP_MISS_ONCE: a pixel whose ray of `sample` misses needs one sample only
 
 
