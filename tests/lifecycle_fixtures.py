@@ -3,12 +3,15 @@ keeps between calls (tests/test_gpu_lifecycle.py compares it across viewport
 sizes; tools/alloc_calls.py counts its allocation calls): the frame and the
 lanes (compute), first_hit's planes and spill, denoise's scratch, both kept
 histories and the merged frame (two keeping reprojects around a camera move),
-sample_map's scratch and compute_map's plan."""
+sample_map's scratch and compute_map's plan, the scaled first-hit planes and
+upsample's outputs (scale 2 from the merged frame after the filter has reused
+its scratch, then scale 3: both grow within one viewport)."""
 import numpy as np
 
 SEED = 0xBABABEBE
 DEPTH = 4
 KEEP = 1  # WPT_REPROJECT_KEEP
+MERGED = 1  # WPT_UPSAMPLE_MERGED
 # the first viewport; one that grows every grow-only buffer, with an odd pixel
 # count (777 pixels: no plane is a multiple of 256 B); one below both
 SIZES = ((24, 16), (37, 21), (8, 8))
@@ -52,8 +55,10 @@ def calls(itf, pkg, vp):
     itf.compute(npx)
     keep("reproject_keep_b", itf.reproject(0, flags=KEEP))
     keep("denoise_merged", itf.denoise_merged())
+    keep("upsample_merged", itf.upsample(2, 0, iterations=3, flags=MERGED))
     count, totals = itf.sample_map(0, target=6, max_per_pixel=4)
     keep("sample_map", [count, np.array(totals, dtype=np.uint64)])
     itf.compute_map(None)
+    keep("upsample", itf.upsample(3, 0, iterations=0))
     keep("read_radiance", itf.read_radiance(*vp))
     return out

@@ -1,10 +1,14 @@
-"""Compares two device assembly listings of wpt_render.hip (`make -C
-wasm-pathtracer_amd/csrc asm` gives build/wpt_render.s) function by function:
-the instructions, the kernel descriptor and the register counts of every
-function of the first listing must be in the second unchanged. Block and
-function label numbers, which shift when a function is added, are ignored.
-Prints the functions only the second listing has; exit 1 on a difference.
-Usage: python3 tools/asm_compare.py PARENT.s NEW.s"""
+"""Compares two sets of device assembly listings (`make -C
+wasm-pathtracer_amd/csrc asm` gives build/wpt_render.s and build/wpt_post.s)
+function by function: the instructions, the kernel descriptor and the register
+counts of every function of the first set must be in the second unchanged.
+Either side is one listing or several, which together must hold each function
+once (a kernel that moved from one unit to another is then compared like any
+other). Block and function label numbers, which shift when a function is added,
+are ignored. Prints the functions only the second set has; exit 1 on a
+difference, a missing function or one that a side holds twice.
+Usage: python3 tools/asm_compare.py PARENT.s NEW.s
+       python3 tools/asm_compare.py PARENT.s [...] -- NEW_A.s NEW_B.s [...]"""
 import re
 import sys
 
@@ -22,6 +26,17 @@ def functions(path):
     return out
 
 
+def side(paths):
+    """The functions of several listings, and the names more than one holds."""
+    out, twice = {}, []
+    for p in paths:
+        for name, body in functions(p).items():
+            if name in out:
+                twice.append(name)
+            out[name] = body
+    return out, twice
+
+
 def norm(body):
     body = re.sub(r"\.LBB\d+_", ".LBB_", body)
     # the loop comments name blocks too, and their column follows the label's
@@ -33,20 +48,31 @@ def norm(body):
 
 
 def main():
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    args = sys.argv[1:]
+    if "--" in args:
+        first, second = args[:args.index("--")], args[args.index("--") + 1:]
+    else:
+        first, second = args[:1], args[1:]
+    if not first or not second:
+        sys.exit(__doc__)
+    (a, twice_a), (b, twice_b) = side(first), side(second)
     missing = [k for k in a if k not in b]
     differ = [k for k in a if k in b and norm(a[k]) != norm(b[k])]
     lines = sum(len(v.splitlines()) for v in a.values())
     print(f"functions: first {len(a)} ({lines} lines), second {len(b)}; identical {len(a) - len(missing) - len(differ)}, "
-          f"different {len(differ)}, missing {len(missing)}")
+          f"different {len(differ)}, missing {len(missing)}, twice in a side {len(twice_a) + len(twice_b)}")
     for k in differ:
         print("DIFFERS", k)
     for k in missing:
         print("MISSING", k)
+    for k in twice_a:
+        print("TWICE in first:", k)
+    for k in twice_b:
+        print("TWICE in second:", k)
     for k in b:
         if k not in a:
             print("only in second:", k)
-    return 1 if differ or missing else 0
+    return 1 if differ or missing or twice_a or twice_b else 0
 
 
 if __name__ == "__main__":

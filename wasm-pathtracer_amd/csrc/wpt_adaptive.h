@@ -374,8 +374,6 @@ __global__ void __launch_bounds__(kBlock) k_plan_round(RoundParams P, const uint
 
 // Exclusive scan of n u32 (in place), three passes: per-block sums, one block
 // scanning the block sums, then each block adds its offset.
-constexpr uint32_t kScanPer = 4;
-constexpr uint32_t kScanChunk = kBlock * kScanPer;
 
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total) {
   __shared__ uint32_t ws[kBlock / 64];

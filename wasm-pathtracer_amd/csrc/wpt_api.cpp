@@ -883,8 +883,11 @@ int wpt_denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t
   if (const char* e = denoise_args(iterations, sigma_c, sigma_z, flags)) return fail(WPT_ERR_INVALID_ARG, e);
   if (const char* e = denoise_plane_args(W, H, acc3, cnt, t, normal3, albedo3, kind)) return fail(WPT_ERR_INVALID_ARG, e);
   std::string err;
-  if (!g_session->renderer.denoise_planes(W, H, acc3, cnt, t, normal3, albedo3, kind, iterations, sigma_c, sigma_z,
-                                          flags, rgb3, valid, rgba, err))
+  Renderer& r = g_session->renderer;
+  Guides g;
+  g.t = t; g.normal = normal3; g.albedo = albedo3; g.kind = kind;
+  if (!r.post().denoise_planes(r.stream(), HostFrame{W, H, acc3, cnt}, g, DnParams{iterations, sigma_c, sigma_z, flags},
+                               PostOut{rgb3, valid, rgba}, err))
     return fail(WPT_ERR_DEVICE, err);
   return WPT_OK;
 }
@@ -992,9 +995,12 @@ int wpt_upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc
                                                          hi_albedo3, hi_kind, background3}))
     return fail(WPT_ERR_INVALID_ARG, e);
   std::string err;
-  if (!g_session->renderer.upsample_planes(W, H, scale, acc3, cnt, t, normal3, albedo3, kind, hi_t, hi_normal3,
-                                           hi_albedo3, hi_kind, background3, iterations, sigma_c, sigma_z, rgb3, valid,
-                                           rgba, err))
+  Renderer& r = g_session->renderer;
+  Guides lo, hi;
+  lo.t = t; lo.normal = normal3; lo.albedo = albedo3; lo.kind = kind;
+  hi.t = hi_t; hi.normal = hi_normal3; hi.albedo = hi_albedo3; hi.kind = hi_kind;
+  if (!r.post().upsample_planes(r.stream(), HostFrame{W, H, acc3, cnt, nullptr, background3}, lo, scale, hi,
+                                DnParams{iterations, sigma_c, sigma_z, 0u}, PostOut{rgb3, valid, rgba}, err))
     return fail(WPT_ERR_DEVICE, err);
   return WPT_OK;
 }
@@ -1026,9 +1032,12 @@ int wpt_reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float*
                                                   h_t, h_id, h_normal3, h_kind}))
     return fail(WPT_ERR_INVALID_ARG, e);
   std::string err;
-  if (!g_session->renderer.reproject_planes(W, H, cam3, acc3, cnt, dir3, t, id, normal3, kind, prev_cam5, h_acc3, h_cnt,
-                                            h_t, h_id, h_normal3, h_kind, cos_min, eps_z, max_len, flags, acc3_out,
-                                            cnt_out, len_out, err))
+  Renderer& r = g_session->renderer;
+  Guides g, hg;
+  g.dir = dir3; g.t = t; g.id = id; g.normal = normal3; g.kind = kind;
+  hg.t = h_t; hg.id = h_id; hg.normal = h_normal3; hg.kind = h_kind;
+  if (!r.post().reproject_planes(r.stream(), HostFrame{W, H, acc3, cnt, cam3}, g, HostFrame{W, H, h_acc3, h_cnt, prev_cam5},
+                                 hg, RpTest{cos_min, eps_z, max_len, flags}, RpHostOut{acc3_out, cnt_out, len_out}, err))
     return fail(WPT_ERR_DEVICE, err);
   return WPT_OK;
 }
@@ -1082,8 +1091,10 @@ int wpt_sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uin
   if (const char* e = sample_map_plane_args(W, H, {cnt, len, kind, member})) return fail(WPT_ERR_INVALID_ARG, e);
   std::string err;
   bool invalid = false;
-  if (!g_session->renderer.sample_map_planes(W, H, cnt, len, kind, member, target, max_per_pixel, budget, flags,
-                                             count_out, total_out, invalid, err))
+  Renderer& r = g_session->renderer;
+  if (!r.post().sample_map_planes(r.stream(), MapPlanes{(uint32_t)((size_t)W * H), cnt, len, kind, member},
+                                  MapParams{target, max_per_pixel, budget, flags}, MapOut{count_out, total_out}, invalid,
+                                  err))
     return fail(invalid ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
   return WPT_OK;
 }

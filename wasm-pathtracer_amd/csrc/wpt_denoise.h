@@ -15,7 +15,7 @@
 //
 // Two parts. The first is plain C++ for host and device: the pack, the weight
 // of one tap, the quantisation, and the host restatement that calls them. The
-// second (WPT_DENOISE_KERNELS, wpt_render.hip) holds the kernels, which call
+// second (WPT_DENOISE_KERNELS, wpt_post.hip) holds the kernels, which call
 // the same functions. Included inside namespace wpt.
 //
 // Kernels, one lane per pixel:

@@ -50,12 +50,6 @@ struct FirstHitParams {
   uint8_t* kind;
 };
 
-__device__ __forceinline__ void st3(float* p, V3 v) {
-  p[0] = v.x;
-  p[1] = v.y;
-  p[2] = v.z;
-}
-
 template <bool TRI_ONLY>
 __global__ void WPT_TRACE_BOUNDS k_first_hit(DevScene S, FirstHitParams P, uint2* __restrict__ spill) {
   __shared__ uint32_t s_code[kLdsSlots * kTBlock];

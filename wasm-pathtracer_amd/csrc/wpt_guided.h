@@ -16,11 +16,13 @@
 // product wraps, and host and device agree on every bit without further care.
 //
 // Two parts. The first is plain C++ for host and device: the two rules and the
-// host restatement that calls them on planes. The second (WPT_GUIDED_KERNELS,
-// wpt_render.hip) holds the kernels, which call the same two functions:
+// host restatement that calls them on planes. The second holds the kernels,
+// which call the same two functions, under two guards so that each is compiled
+// in one unit: the planning kernels (WPT_GUIDED_KERNELS, wpt_post.hip) are
 // k_map_need, a three-pass exclusive scan of u64 (the shape of k_scan_local /
-// k_scan_sums / k_scan_add, wpt_adaptive.h), k_map_deal, and k_map_plan for the
-// tracing call. Included inside namespace wpt, after wpt_reproject.h.
+// k_scan_sums / k_scan_add, wpt_adaptive.h) and k_map_deal; k_map_plan
+// (WPT_GUIDED_PLAN_KERNEL, wpt_render.hip) belongs to the tracing call.
+// Included inside namespace wpt, after wpt_reproject.h.
 #pragma once
 
 constexpr uint32_t kMapMissOnce = 1u;  // WPT_MAP_MISS_ONCE
@@ -161,6 +163,10 @@ __global__ void __launch_bounds__(kBlock) k_map_deal(uint32_t np, const u64* __r
   count[i] = map_deal(pre[i], pre[i + 1], budget, pre[np]);
 }
 
+#endif  // WPT_GUIDED_KERNELS
+
+#if defined(WPT_GUIDED_PLAN_KERNEL)
+
 // The plan of a batch that traces a sample map: per partition entry p its
 // pixel's count (then, scanned, its first position) and base = the pixel's
 // sample count, the next unused sample index; off[npart] = 0 is the scan's
@@ -191,4 +197,4 @@ __global__ void __launch_bounds__(kBlock) k_map_plan(const uint32_t* __restrict_
   if ((threadIdx.x & 63) == 0 && s != 0ull) atomicAdd(words, s);
 }
 
-#endif  // WPT_GUIDED_KERNELS
+#endif  // WPT_GUIDED_PLAN_KERNEL

@@ -15,6 +15,7 @@
 
 #include "wpt_devmem.h"
 #include "wpt_photon.h"
+#include "wpt_post.h"
 #include "wpt_scene.h"
 #include "wpt_seqsum.h"
 
@@ -320,7 +321,8 @@ class Renderer {
   // the same planes for the virtual viewport scale * width x scale * height
   // under the session's camera and seed (wpt_first_hit_scaled), in a buffer of
   // its own: first_hit's, which the filter, the reprojection and the sample map
-  // leave their guides in, is not written. The caller checks scale.
+  // leave their guides in, is not written. The caller checks scale (0 here is
+  // first_hit itself: the session's viewport, first_hit's buffer).
   bool first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits,
                         float* normal3, float* albedo3, uint8_t* kind, std::string& err);
   // guided upsampling (wpt_upsample.h) of the session's frame, or with
@@ -330,42 +332,24 @@ class Renderer {
   // `sample`; a null output is not written
   bool upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
                 float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
-  // test hook: the same kernels and launch geometry on a caller's planes
-  bool upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt, const float* t,
-                       const float* normal3, const float* albedo3, const uint8_t* kind, const float* hi_t,
-                       const float* hi_normal3, const float* hi_albedo3, const uint8_t* hi_kind,
-                       const float* background3, uint32_t iterations, float sigma_c, float sigma_z, float* rgb3,
-                       uint8_t* valid, uint8_t* rgba, std::string& err);
   // the a-trous filter (wpt_denoise.h) on the session's frame, guided by the
   // first-hit planes of `sample` (wpt_denoise); a null output is not written
   bool denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
                uint8_t* valid, uint8_t* rgba, std::string& err);
-  // test hook: the same kernels and launch geometry on a caller's planes
-  bool denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
-                      const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
-                      float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba,
-                      std::string& err);
   // reverse reprojection of the kept history into the current camera, merged
   // with the session's frame (wpt_reproject.h, wpt_reproject); a null output is
   // not written. keep: the merged frame, the planes of `sample` and the camera
   // become the history. The caller checks history_state() != 2 first.
   bool reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
                  uint32_t* cnt, uint32_t* len, std::string& err);
-  // test hook: k_reproject and its launch geometry on a caller's planes
-  bool reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
-                        const float* dir3, const float* t, const int32_t* id, const float* normal3,
-                        const uint8_t* kind, const float* prev_cam5, const float* h_acc3, const uint32_t* h_cnt,
-                        const float* h_t, const int32_t* h_id, const float* h_normal3, const uint8_t* h_kind,
-                        float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3_out,
-                        uint32_t* cnt_out, uint32_t* len_out, std::string& err);
   // the a-trous filter over the merged frame and the guide planes the last
   // reproject of this viewport left on the device (wpt_denoise_merged)
-  bool has_merged() const { return rp_merged_; }
+  bool has_merged() const { return post_.has_merged(); }
   bool denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
                       uint8_t* rgba, std::string& err);
   // WPT_OPT_HISTORY: 0 no history, 1 usable, 2 kept in the current accumulation
-  int history_state() const { return hist_cur_ < 0 ? 0 : hist_epoch_ == epoch_ ? 2 : 1; }
-  void history_drop() { hist_cur_ = -1; }
+  int history_state() const { return post_.history_state(epoch_); }
+  void history_drop() { post_.history_drop(); }
   // Guided sampling (wpt_guided.h). sample_map: the map planned from the
   // counts, the len plane of this accumulation's last reproject and (under
   // WPT_MAP_MISS_ONCE) the first-hit kinds of `sample`; it stays on the device
@@ -374,10 +358,6 @@ class Renderer {
   // caller's argument (WPT_ERR_INVALID_ARG), nothing was traced or kept.
   bool sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
                   uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err);
-  // test hook: the same kernels and launch geometry on a caller's planes
-  bool sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
-                         const uint8_t* member, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
-                         uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err);
   bool compute_map(const uint32_t* count, bool& invalid, std::string& err);
   // WPT_OPT_MAP_MODE: a map was traced in this accumulation (wpt_compute is an
   // error until the next reset)
@@ -438,6 +418,8 @@ class Renderer {
   uint32_t part_pixels() const { return (uint32_t)part_pix_.size(); }
   const std::vector<uint32_t>& part_list() const { return part_pix_; }
   hipStream_t stream() const { return stream_; }
+  // the frame post-processing; its *_planes test hooks need stream() and nothing else of the session
+  FramePost& post() { return post_; }
   uint32_t bvh_depth() const { return depth_; }
 
  private:
@@ -517,7 +499,7 @@ class Renderer {
   void free_scene();
   void free_paths();
   void free_photons();
-  void free_frame();       // the viewport's frame buffers and denoise's scratch
+  void free_frame();       // the viewport's frame buffers and the scaled first-hit planes
   void free_partition();   // the pixel lists, the exchange index, compute_map's plan
   void free_stock_side();  // the ring's side buffers and the refill pool (not the ring)
   bool upload_photons(const PhotonTree& tree, std::string& err);
@@ -731,64 +713,25 @@ class Renderer {
   // planes; the traversal-stack spill area of its grid
   DevBuf<char> d_fh_;
   DevBuf<uint2> d_fh_spill_;
-  // k_first_hit of the planes in `mask` into d_fh_ (plane k at off[k]); waits
-  // for it. scale != 0: the virtual viewport scale * w_ x scale * h_, into d_fhs_.
-  bool first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err, uint32_t scale = 0);
-  // the scaled planes' buffer (first_hit_scaled, upsample's fine guides) and
-  // upsample's outputs; made on first use, freed with the viewport
+  // k_first_hit of the planes in `mask` into d_fh_; waits for it. scale != 0:
+  // the virtual viewport scale * w_ x scale * h_, into d_fhs_ (first_hit_scaled,
+  // upsample's fine guides; made on first use, freed with the viewport).
+  struct FhPlanes : Guides {
+    const uint32_t* visits = nullptr;
+  };
+  bool first_hit_launch(uint32_t sample, uint32_t mask, FhPlanes& planes, std::string& err, uint32_t scale = 0);
   DevBuf<char> d_fhs_;
-  DevBuf<char> d_up_;
-  // denoise's scratch for the session's viewport (records A0, A1, B, a' and
-  // the outputs), made on first use, freed with the viewport; the filter
-  // itself over device planes in a scratch of dn_bytes(W * H)
-  DevBuf<char> d_dn_;
-  static size_t dn_bytes(size_t np);
-  bool dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
-              const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
-              float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
-  // dn_run's first half, which upsample shares: pack and the passes, queued on
-  // lane 0's stream; the result is record plane `cur` (0: A0, 1: A1) beside B and a'
-  bool dn_passes(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t, const float* normal,
-                 const float* albedo, const uint8_t* kind, char* scratch, uint32_t iterations, float sigma_c,
-                 float sigma_z, uint32_t flags, int& cur, std::string& err);
-  // k_upsample over the records dn_passes left in dn_scratch (plane cur) and
-  // fine device planes, outputs in up_scratch (up_bytes(fine pixels)), copied
-  // to the host and waited for
-  static size_t up_bytes(size_t nf);
-  bool up_run(uint32_t W, uint32_t H, uint32_t scale, const char* dn_scratch, int cur, const float* hi_t,
-              const float* hi_normal, const float* hi_albedo, const uint8_t* hi_kind, const float bg[3], float sigma_z,
-              char* up_scratch, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err);
-  uint32_t dn_lds_ = 7;  // WPT_OPT_DENOISE_LDS
-  // Reprojection. epoch_ counts the resets of the accumulation (reset() is the
-  // one place each passes through); a history kept at the current epoch already
-  // holds the current samples. d_hist_: the two kept frames, ping-ponged (a
-  // keeping call reads one and writes the other), hist_cur_ the live one or -1;
-  // d_rp_: the merged frame and the guide planes of the last call. All made on
-  // first use and freed with the viewport.
-  uint64_t epoch_ = 0, hist_epoch_ = 0;
-  int hist_cur_ = -1;
-  float hist_cam_[5] = {0, 0, 0, 0, 0};
-  DevBuf<char> d_hist_[2];
-  DevBuf<char> d_rp_;
-  bool rp_merged_ = false;
-  uint64_t rp_epoch_ = 0;  // the accumulation d_rp_'s len plane belongs to (sample_map reads it in that one only)
-  void free_reproject();
-  // Guided sampling. d_map_: sample_map's scratch and the map it leaves (made
-  // on first use, freed with the viewport), valid in the accumulation map_epoch_
-  // while map_ok_; d_mplan_: compute_map's uploaded map, offsets, bases, scan
-  // sums and words (freed with the partition). map_mode_: reset() clears it.
-  DevBuf<char> d_map_;
-  bool map_ok_ = false;
-  uint64_t map_epoch_ = 0;
+  // The filter, the reprojection, the upsampling and the sample map's planning
+  // with the state they keep between calls (wpt_post.h). post_ knows nothing of
+  // the session: frame_ref() is what it is told of the frame. epoch_ counts the
+  // resets of the accumulation (reset() is the one place each passes through).
+  FramePost post_;
+  FrameRef frame_ref() const { return FrameRef{w_, h_, d_acc_, d_cnt_, cam_, ds_.bg, epoch_, stream_}; }
+  uint64_t epoch_ = 0;
+  // compute_map's uploaded map, offsets, bases, scan sums and words (freed with
+  // the partition). map_mode_: reset() clears it.
   DevBuf<char> d_mplan_;
   bool map_mode_ = false;
-  void free_guided();
-  // the kernels of sample_map over device planes (null len / kind / member: see
-  // k_map_need) in a scratch of MapLayout(np); T comes back, the deal is
-  // launched only if it is below 2^32
-  bool map_run(uint32_t np, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind, const uint8_t* member,
-               char* scratch, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags, uint32_t* count_out,
-               uint64_t* total_out, bool& invalid, std::string& err);
   bool compute_end(std::string& err);  // what every tracing call ends with: counts, overflow flag, work counters
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];

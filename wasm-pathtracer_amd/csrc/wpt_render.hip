@@ -10,6 +10,7 @@
 // an iterative stack machine with identical cull / order / tie rules, so the
 // closest hit (t, shape id) is bit-identical to the reference's.
 #include "wpt_render.h"
+#include "wpt_launch.h"
 #include "wpt_partition.h"
 #include "wpt_photon.h"
 #include "wpt_quartic.h"
@@ -28,15 +29,6 @@
 #include <thread>
 #include <type_traits>
 
-#define HIP_OK(expr)                                                     \
-  do {                                                                   \
-    hipError_t e_ = (expr);                                              \
-    if (e_ != hipSuccess) {                                              \
-      err = std::string(#expr " failed: ") + hipGetErrorString(e_);      \
-      return false;                                                      \
-    }                                                                    \
-  } while (0)
-
 // WPT_OPT_LOG lines, stamped with the host's monotonic clock in ms (Python's
 // time.monotonic() on Linux: tools/session_rate.py marks its calls with it)
 static double wpt_log_ms() {
@@ -48,7 +40,6 @@ namespace wpt {
 
 namespace {
 
-constexpr uint32_t kBlock = 256;
 // Threads per block of the traversal kernels (k_extend, k_shadow, k_trace,
 // k_finish): their LDS stack (kLdsSlots entries per lane) and the LDS
 // treelet are per block, so larger blocks hold one treelet for more lanes.
@@ -957,7 +948,6 @@ using ShadeFields = Fields<10, kShadeBlock>;
 // lanes from COLS - 1 on of wave 0 each add to a 64-bit counter of their own.
 // s_off[c][w]: wave w's count in column c, then (after reserve) the range
 // entry its first lane writes. COLS: the block's waves (times k_generate_ps's tiles).
-using u64 = unsigned long long;
 template <uint32_t N, uint32_t COLS>
 struct BlockAppend {
   static constexpr uint32_t kCols = COLS;
@@ -2546,8 +2536,6 @@ __global__ void k_pack_partition(const uint32_t* __restrict__ part_pix, uint32_t
   out[i] = a;
 }
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
 // The exclusive u32 scan of data[0 .. n) in place, in chunks of kScanChunk:
 // `sums` holds a word per chunk. The caller checks hipGetLastError.
 inline void scan_u32(hipStream_t stream, uint32_t* data, uint32_t n, uint32_t* sums) {
@@ -2555,32 +2543,6 @@ inline void scan_u32(hipStream_t stream, uint32_t* data, uint32_t n, uint32_t* s
   k_scan_local<<<nb, kBlock, 0, stream>>>(data, n, sums);
   k_scan_sums<<<1, kBlock, 0, stream>>>(sums, nb);
   k_scan_add<<<nb, kBlock, 0, stream>>>(data, n, sums);
-}
-
-// n host rgb triples as float4 (w = 0) to dst, queued on s from `stage`, which
-// the caller keeps until it has waited for s.
-inline hipError_t upload_rgb3(hipStream_t s, const float* rgb3, size_t n, std::vector<float4>& stage, float4* dst) {
-  stage.resize(n);
-  for (size_t i = 0; i < n; i++) stage[i] = make_float4(rgb3[3 * i], rgb3[3 * i + 1], rgb3[3 * i + 2], 0.0f);
-  return hipMemcpyAsync(dst, stage.data(), sizeof(float4) * n, hipMemcpyHostToDevice, s);
-}
-
-// The xyz of n device float4 into host rgb triples: queued on s, then waits
-// for s (and with it for the copies the caller queued before). A null rgb3
-// only waits.
-inline hipError_t download_rgb3(hipStream_t s, const float4* src, size_t n, float* rgb3) {
-  std::vector<float4> a(rgb3 ? n : 0);
-  if (rgb3) {
-    const hipError_t e = hipMemcpyAsync(a.data(), src, sizeof(float4) * n, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-  }
-  const hipError_t e = hipStreamSynchronize(s);
-  for (size_t i = 0; i < a.size(); i++) {
-    rgb3[3 * i] = a[i].x;
-    rgb3[3 * i + 1] = a[i].y;
-    rgb3[3 * i + 2] = a[i].z;
-  }
-  return e;
 }
 
 // n shadow rays p -> q towards `light` as the shadow stream holds them: (origin,
@@ -2601,13 +2563,12 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 }
 
 #include "wpt_first_hit.h"
-#define WPT_DENOISE_KERNELS
+// the post-processing's flags; its kernels are wpt_post.hip's, but for
+// compute_map's k_map_plan
 #include "wpt_denoise.h"
-#define WPT_REPROJECT_KERNELS
 #include "wpt_reproject.h"
-#define WPT_GUIDED_KERNELS
+#define WPT_GUIDED_PLAN_KERNEL
 #include "wpt_guided.h"
-#define WPT_UPSAMPLE_KERNELS
 #include "wpt_upsample.h"
 
 }  // namespace
@@ -2719,7 +2680,7 @@ Renderer::~Renderer() {
   free_paths();
   free_partition();
   free_frame();
-  free_reproject();
+  post_.release(FramePost::Sized::kViewport);
   d_work_.reset();
   d_probe_.reset();
   d_fallback_.reset();
@@ -3060,7 +3021,7 @@ bool Renderer::set_option(int opt, int64_t v, std::string& err) {
     case 38: if (!range(0, 1)) return false; drop_miss_ = v != 0; return true;
     case 39: if (!range(0, 1)) return false; presolve_shadow_ = v != 0; return true;
     case 40: if (!range(0, 1)) return false; gen_shade_ = v != 0; return true;
-    case 45: if (!range(0, 7)) return false; dn_lds_ = (uint32_t)v; return true;
+    case 45: if (!range(0, 7)) return false; post_.set_dn_lds((uint32_t)v); return true;
     case 26:
       if (!range(0, 1)) return false;
       if (!drain_async(err)) return false;  // a batch keeps its stream
@@ -3121,7 +3082,7 @@ bool Renderer::get_option(int opt, int64_t& v) const {
     case 38: v = drop_miss_ ? 1 : 0; return true;
     case 39: v = presolve_shadow_ ? 1 : 0; return true;
     case 40: v = gen_shade_ ? 1 : 0; return true;
-    case 45: v = dn_lds_; return true;
+    case 45: v = post_.dn_lds(); return true;
     case 26: v = async_prio_; return true;
     case 27: v = async_grid_pct_; return true;
     // read-only: what the uploaded scene's traversal kernels run:
@@ -3143,16 +3104,14 @@ bool Renderer::get_option(int opt, int64_t& v) const {
   }
 }
 
-// The viewport's frame and the scratch sized by it (the history and the merged
-// frame: free_reproject).
+// The viewport's frame and the scaled first-hit planes (what the
+// post-processing sized by the viewport: post_.release, which follows it).
 void Renderer::free_frame() {
   d_acc_.reset();
   d_cnt_.reset();
   d_rgba_.reset();
   d_samp_.reset();
-  d_dn_.reset();
   d_fhs_.reset();
-  d_up_.reset();
 }
 
 // The partition's pixel lists and what is sized by them.
@@ -3167,7 +3126,8 @@ void Renderer::free_partition() {
     half_npix_[k] = seam_npix_[k] = rest_npix_[k] = 0;
   }
   maxpart_ = 0;
-  free_guided();
+  post_.release(FramePost::Sized::kPartition);
+  d_mplan_.reset();
 }
 
 bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
@@ -3180,7 +3140,7 @@ bool Renderer::set_viewport(uint32_t w, uint32_t h, std::string& err) {
   h_ = h;
   free_rounds();
   free_frame();
-  free_reproject();
+  post_.release(FramePost::Sized::kViewport);
   HIP_OK(d_acc_.alloc((size_t)w * h));
   HIP_OK(d_cnt_.alloc((size_t)w * h));
   HIP_OK(d_rgba_.alloc(4 * (size_t)w * h));
@@ -5350,21 +5310,10 @@ bool Renderer::trace_rays(size_t n, const float* rays, float* t_out, int32_t* id
 // timings are neither read nor written.
 bool Renderer::first_hit(uint32_t sample, float* dir3, float* t, int32_t* id, uint32_t* visits, float* normal3,
                          float* albedo3, uint8_t* kind, std::string& err) {
-  const uint32_t mask = (dir3 ? kFhDir : 0u) | (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) |
-                        (normal3 ? kFhNormal : 0u) | (albedo3 ? kFhAlbedo : 0u) | (kind ? kFhKind : 0u);
-  if (!scene_ok_) { err = "no scene"; return false; }
-  if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
-  if (mask == 0) return true;
-  size_t off[7];
-  if (!first_hit_launch(sample, mask, off, err)) return false;
-  const size_t np = (size_t)w_ * h_;
-  void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
-  for (int k = 0; k < 7; k++)
-    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], (char*)d_fh_ + off[k], kFhElem[k] * np, hipMemcpyDeviceToHost, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  return true;
+  return first_hit_scaled(0, sample, dir3, t, id, visits, normal3, albedo3, kind, err);
 }
 
+// scale 0: first_hit's planes at the session's viewport, in d_fh_.
 bool Renderer::first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, float* t, int32_t* id,
                                 uint32_t* visits, float* normal3, float* albedo3, uint8_t* kind, std::string& err) {
   const uint32_t mask = (dir3 ? kFhDir : 0u) | (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) |
@@ -5372,12 +5321,13 @@ bool Renderer::first_hit_scaled(uint32_t scale, uint32_t sample, float* dir3, fl
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   if (mask == 0) return true;
-  size_t off[7];
-  if (!first_hit_launch(sample, mask, off, err, scale)) return false;
-  const size_t np = (size_t)scale * w_ * ((size_t)scale * h_);
+  FhPlanes P;
+  if (!first_hit_launch(sample, mask, P, err, scale)) return false;
+  const size_t np = scale ? (size_t)scale * w_ * ((size_t)scale * h_) : (size_t)w_ * h_;
   void* host[7] = {dir3, t, id, visits, normal3, albedo3, kind};
+  const void* dev[7] = {P.dir, P.t, P.id, P.visits, P.normal, P.albedo, P.kind};
   for (int k = 0; k < 7; k++)
-    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], (char*)d_fhs_ + off[k], kFhElem[k] * np, hipMemcpyDeviceToHost, stream_));
+    if (host[k]) HIP_OK(hipMemcpyAsync(host[k], dev[k], kFhElem[k] * np, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   return true;
 }
@@ -5399,18 +5349,18 @@ static_assert(FhLayout(1000, 0x40u).bytes == 1280 && FhLayout(1000, 0x40u).off[6
 }  // namespace
 
 // k_first_hit of the planes in `mask` (bit k = plane k of wpt_first_hit's
-// order) into d_fh_, plane k at byte off[k]; returns once the kernel has ended
-// without a stack overflow. scale != 0: the planes of the virtual viewport
-// scale * w_ x scale * h_ (the camera, the seed and so the field of view are the
-// session's; the caller checks that it has fewer than 2^32 pixels), into d_fhs_.
-bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], std::string& err, uint32_t scale) {
+// order) into d_fh_; `planes` gets the device pointers of those planes (null:
+// not in the mask); returns once the kernel has ended without a stack overflow.
+// scale != 0: the planes of the virtual viewport scale * w_ x scale * h_ (the
+// camera, the seed and so the field of view are the session's; the caller
+// checks that it has fewer than 2^32 pixels), into d_fhs_.
+bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, FhPlanes& planes, std::string& err, uint32_t scale) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0) { err = "no viewport"; return false; }
   const uint32_t vw = scale ? scale * w_ : w_, vh = scale ? scale * h_ : h_;
   DevBuf<char>& buf = scale ? d_fhs_ : d_fh_;
   const size_t np = (size_t)vw * vh;
   const FhLayout Z(np, mask);
-  std::copy(Z.off, Z.off + 7, off);
   HIP_OK(buf.grow(Z.bytes));
   FirstHitParams P;
   P.G = gen_params((uint32_t)np, scale ? scale : 1u);
@@ -5419,13 +5369,21 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
   P.tiles_x = (vw + kFhTile - 1) / kFhTile;
   P.ntiles = P.tiles_x * ((vh + kFhTile - 1) / kFhTile);
   char* base = buf;
-  P.dir = (float*)(base + off[0]);
-  P.t = (float*)(base + off[1]);
-  P.id = (int32_t*)(base + off[2]);
-  P.visits = (uint32_t*)(base + off[3]);
-  P.normal = (float*)(base + off[4]);
-  P.albedo = (float*)(base + off[5]);
-  P.kind = (uint8_t*)(base + off[6]);
+  P.dir = (float*)(base + Z.off[0]);
+  P.t = (float*)(base + Z.off[1]);
+  P.id = (int32_t*)(base + Z.off[2]);
+  P.visits = (uint32_t*)(base + Z.off[3]);
+  P.normal = (float*)(base + Z.off[4]);
+  P.albedo = (float*)(base + Z.off[5]);
+  P.kind = (uint8_t*)(base + Z.off[6]);
+  planes = FhPlanes();
+  if (mask & kFhDir) planes.dir = P.dir;
+  if (mask & kFhT) planes.t = P.t;
+  if (mask & kFhId) planes.id = P.id;
+  if (mask & kFhVisits) planes.visits = P.visits;
+  if (mask & kFhNormal) planes.normal = P.normal;
+  if (mask & kFhAlbedo) planes.albedo = P.albedo;
+  if (mask & kFhKind) planes.kind = P.kind;
   // one block per kTBlock / 64 tiles, clamped to a spill area of kFhSpillBytes
   // (deep trees: the blocks then take further tiles a grid stride on)
   constexpr size_t kFhSpillBytes = 256ull << 20;
@@ -5448,475 +5406,78 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, size_t off[7], s
 }
 
 // ---------------------------------------------------------------------------
-// The a-trous filter (wpt_denoise.h)
+// Frame post-processing (wpt_post.h): the session's entry points check the
+// scene and the viewport, make the guide planes of `sample` with k_first_hit
+// (they stay on the device) and hand the frame as this rank holds it to post_,
+// which queues on lane 0's stream, the main one. The frame, the counts, the
+// rounds, the stock and the counters are only read.
 // ---------------------------------------------------------------------------
 
-// Scratch of a frame of np pixels: the records A0, A1 and B, a', then the
-// outputs rgb, rgba and valid; every part 256 B aligned.
-namespace {
-struct DnLayout {
-  size_t a0 = 0, a1 = 0, b = 0, ap = 0, rgb = 0, rgba = 0, valid = 0, bytes = 0;
-  constexpr explicit DnLayout(size_t np) {
-    Slices z;
-    a0 = z.take(16 * np); a1 = z.take(16 * np); b = z.take(16 * np); ap = z.take(12 * np); rgb = z.take(12 * np);
-    rgba = z.take(4 * np); valid = z.take(np);
-    bytes = z.at;
-  }
-};
-static_assert(DnLayout(1000).bytes == 77568 && DnLayout(1000).valid == 76544 && DnLayout(1000).ap == 48384,
-              "denoise's layout");
+constexpr uint32_t kFhGuides = kFhT | kFhNormal | kFhAlbedo | kFhKind;  // what the filter reads
 
-template <int STEP>
-void launch_atrous(bool lds, dim3 grid, hipStream_t s, const float4* A, const float4* B, uint32_t W, uint32_t H,
-                   float s2, float sigma_z, float4* Aout) {
-  if constexpr (STEP <= 4) {
-    if (lds) {
-      k_dn_atrous<STEP, true><<<grid, kBlock, 0, s>>>(A, B, W, H, s2, sigma_z, Aout);
-      return;
-    }
-  }
-  k_dn_atrous<STEP, false><<<grid, kBlock, 0, s>>>(A, B, W, H, s2, sigma_z, Aout);
-}
-}  // namespace
-
-size_t Renderer::dn_bytes(size_t np) { return DnLayout(np).bytes; }
-
-// Pack and the iterations over device planes, queued on lane 0's stream,
-// neither timed nor counted; the filtered records are plane `cur` of the
-// scratch. Iteration i runs the LDS kernel if bit i of WPT_OPT_DENOISE_LDS is
-// set (steps 1, 2, 4 only), else the direct one.
-bool Renderer::dn_passes(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
-                         const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
-                         uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, int& cur,
-                         std::string& err) {
-  hipStream_t s = lane0_ctx(false).stream;
-  const size_t np = (size_t)W * H;
-  const DnLayout Z(np);
-  float4* A[2] = {(float4*)(scratch + Z.a0), (float4*)(scratch + Z.a1)};
-  float4* B = (float4*)(scratch + Z.b);
-  float* ap = (float*)(scratch + Z.ap);
-  k_dn_pack<<<blocks_for(np), kBlock, 0, s>>>(acc, cnt, t, normal, albedo, kind, (uint32_t)np, flags, A[0], B, ap);
-  HIP_OK(hipGetLastError());
-  const dim3 grid((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile);
-  float sig = sigma_c;
-  cur = 0;
-  for (uint32_t i = 0; i < iterations; i++) {
-    const float s2 = sig * sig;
-    const bool lds = (dn_lds_ >> i & 1u) != 0;
-    switch (i) {
-      case 0: launch_atrous<1>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
-      case 1: launch_atrous<2>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
-      case 2: launch_atrous<4>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
-      case 3: launch_atrous<8>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
-      default: launch_atrous<16>(lds, grid, s, A[cur], B, W, H, s2, sigma_z, A[cur ^ 1]); break;
-    }
-    HIP_OK(hipGetLastError());
-    cur ^= 1;
-    sig = sig * 0.5f;
-  }
-  return true;
-}
-
-// The filter over device planes: dn_passes, then unpack; the outputs wanted
-// are copied to the host and waited for.
-bool Renderer::dn_run(uint32_t W, uint32_t H, const float4* acc, const uint32_t* cnt, const float* t,
-                      const float* normal, const float* albedo, const uint8_t* kind, char* scratch,
-                      uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
-                      uint8_t* rgba, std::string& err) {
-  int cur = 0;
-  if (!dn_passes(W, H, acc, cnt, t, normal, albedo, kind, scratch, iterations, sigma_c, sigma_z, flags, cur, err))
-    return false;
-  hipStream_t s = lane0_ctx(false).stream;
-  const size_t np = (size_t)W * H;
-  const DnLayout Z(np);
-  const float4* A = (const float4*)(scratch + (cur ? Z.a1 : Z.a0));
-  const float4* B = (const float4*)(scratch + Z.b);
-  const float* ap = (const float*)(scratch + Z.ap);
-  float* d_rgb = rgb3 ? (float*)(scratch + Z.rgb) : nullptr;
-  uint8_t* d_rgba = rgba ? (uint8_t*)(scratch + Z.rgba) : nullptr;
-  uint8_t* d_valid = valid ? (uint8_t*)(scratch + Z.valid) : nullptr;
-  k_dn_unpack<<<blocks_for(np), kBlock, 0, s>>>(A, B, ap, (uint32_t)np, d_rgb, d_valid, d_rgba);
-  HIP_OK(hipGetLastError());
-  if (rgb3) HIP_OK(hipMemcpyAsync(rgb3, d_rgb, 12 * np, hipMemcpyDeviceToHost, s));
-  if (valid) HIP_OK(hipMemcpyAsync(valid, d_valid, np, hipMemcpyDeviceToHost, s));
-  if (rgba) HIP_OK(hipMemcpyAsync(rgba, d_rgba, 4 * np, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return true;
-}
-
-// The session's frame as this rank holds it, guided by k_first_hit's planes
-// of `sample`, which stay on the device. The frame, the counts, the rounds,
-// the stock and the counters are only read.
 bool Renderer::denoise(uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags,
                        float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
   if (!rgb3 && !valid && !rgba) return true;
-  size_t off[7];
-  if (!first_hit_launch(sample, kFhT | kFhNormal | kFhAlbedo | kFhKind, off, err)) return false;
-  HIP_OK(d_dn_.grow(dn_bytes((size_t)w_ * h_)));
-  const char* fh = d_fh_;
-  return dn_run(w_, h_, d_acc_, d_cnt_, (const float*)(fh + off[1]), (const float*)(fh + off[4]),
-                (const float*)(fh + off[5]), (const uint8_t*)(fh + off[6]), d_dn_, iterations, sigma_c, sigma_z,
-                flags, rgb3, valid, rgba, err);
+  FhPlanes g;
+  if (!first_hit_launch(sample, kFhGuides, g, err)) return false;
+  return post_.denoise(frame_ref(), g, DnParams{iterations, sigma_c, sigma_z, flags}, PostOut{rgb3, valid, rgba}, err);
 }
 
-bool Renderer::denoise_planes(uint32_t W, uint32_t H, const float* acc3, const uint32_t* cnt, const float* t,
-                              const float* normal3, const float* albedo3, const uint8_t* kind, uint32_t iterations,
-                              float sigma_c, float sigma_z, uint32_t flags, float* rgb3, uint8_t* valid,
-                              uint8_t* rgba, std::string& err) {
-  if (!stream_) { err = "no device"; return false; }
-  if (!rgb3 && !valid && !rgba) return true;
-  const size_t np = (size_t)W * H;
-  HookScratch S;
-  float4* d_acc = S.d<float4>(np);
-  uint32_t* d_cnt = S.d<uint32_t>(np);
-  float* d_t = S.d<float>(np);
-  float* d_n = S.d<float>(3 * np);
-  float* d_al = S.d<float>(3 * np);
-  uint8_t* d_kind = S.d<uint8_t>(np);
-  char* scratch = S.d<char>(dn_bytes(np));
-  if (!S.ok) { err = "hipMalloc failed (denoise_planes)"; return false; }
-  std::vector<float4> a4;
-  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
-  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_t, t, sizeof(float) * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_al, albedo3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  return dn_run(W, H, d_acc, d_cnt, d_t, d_n, d_al, d_kind, scratch, iterations, sigma_c, sigma_z, flags, rgb3, valid,
-                rgba, err);
+bool Renderer::denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
+                              uint8_t* valid, uint8_t* rgba, std::string& err) {
+  return post_.denoise_merged(frame_ref(), DnParams{iterations, sigma_c, sigma_z, flags}, PostOut{rgb3, valid, rgba},
+                              err);
 }
 
-// ---------------------------------------------------------------------------
-// Reprojection of a kept frame (wpt_reproject.h)
-// ---------------------------------------------------------------------------
-
-namespace {
-// Parts of np pixels, each 256 B aligned: a kept frame's planes, and the merged
-// frame with the guide planes dn_run reads.
-struct RpHistLayout {
-  size_t k = 0, r0 = 0, r1 = 0, id = 0, bytes = 0;
-  constexpr explicit RpHistLayout(size_t np) {
-    Slices z;
-    r0 = z.take(16 * np); r1 = z.take(16 * np); k = z.take(4 * np); id = z.take(4 * np);
-    bytes = z.at;
-  }
-  RpHist at(void* base) const {
-    char* b = (char*)base;
-    RpHist h;
-    h.k = (uint32_t*)(b + k); h.r0 = (float4*)(b + r0); h.r1 = (float4*)(b + r1); h.id = (int32_t*)(b + id);
-    return h;
-  }
-};
-static_assert(RpHistLayout(1000).bytes == 40448 && RpHistLayout(1000).k == 32256 && RpHistLayout(1000).id == 36352,
-              "the kept frame's layout");
-struct RpMergedLayout {
-  size_t acc = 0, cnt = 0, len = 0, t = 0, normal = 0, albedo = 0, kind = 0, bytes = 0;
-  constexpr explicit RpMergedLayout(size_t np) {
-    Slices z;
-    acc = z.take(16 * np); cnt = z.take(4 * np); len = z.take(4 * np); t = z.take(4 * np); normal = z.take(12 * np);
-    albedo = z.take(12 * np); kind = z.take(np);
-    bytes = z.at;
-  }
-};
-static_assert(RpMergedLayout(1000).bytes == 53504 && RpMergedLayout(1000).len == 20224 &&
-                  RpMergedLayout(1000).kind == 52480,
-              "the merged frame's layout");
-const RpHist kNoHist = {nullptr, nullptr, nullptr, nullptr};
-}  // namespace
-
-void Renderer::free_reproject() {
-  d_hist_[0].reset();
-  d_hist_[1].reset();
-  d_rp_.reset();
-  hist_cur_ = -1;
-  rp_merged_ = false;
-}
-
-// The session's frame as this rank holds it, merged with the kept history
-// through k_first_hit's planes of `sample`, which stay on the device; on lane
-// 0's stream like the filter, neither timed nor counted. The frame, the counts,
-// the rounds, the stock and the counters are only read. The merged frame and
-// the guide planes stay in d_rp_ for denoise_merged.
 bool Renderer::reproject(uint32_t sample, float cos_min, float eps_z, uint32_t max_len, uint32_t flags, float* acc3,
                          uint32_t* cnt, uint32_t* len, std::string& err) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
   const bool keep = (flags & kRpKeep) != 0;
   if (!acc3 && !cnt && !len && !keep) return true;
-  const bool need_id = keep || ((flags & kRpSameShape) && hist_cur_ >= 0);
-  size_t off[7];
-  if (!first_hit_launch(sample, kFhDir | kFhT | kFhNormal | kFhAlbedo | kFhKind | (need_id ? kFhId : 0u), off, err))
-    return false;
-  const size_t np = (size_t)w_ * h_;
-  const RpMergedLayout M(np);
-  const RpHistLayout HL(np);
-  HIP_OK(d_rp_.grow(M.bytes));
-  const int into = hist_cur_ == 0 ? 1 : 0;  // the kept frame not being read
-  if (keep) HIP_OK(d_hist_[into].grow(HL.bytes));
-  rp_merged_ = false;
-  const char* fh = d_fh_;
-  char* m = d_rp_;
-  RpParams P;
-  P.A.W = w_; P.A.H = h_;
-  P.A.cam = mk(cam_[0], cam_[1], cam_[2]);
-  P.A.V = rp_view(w_, h_, hist_cam_);
-  P.A.cos_min = cos_min; P.A.eps_z = eps_z; P.A.max_len = max_len; P.A.flags = flags;
-  P.npix = (uint32_t)np;
-  P.acc = d_acc_;
-  P.cnt = d_cnt_;
-  P.dir = (const float*)(fh + off[0]);
-  P.t = (const float*)(fh + off[1]);
-  P.id = need_id ? (const int32_t*)(fh + off[2]) : nullptr;
-  P.normal = (const float*)(fh + off[4]);
-  P.kind = (const uint8_t*)(fh + off[6]);
-  P.hist = hist_cur_ >= 0 ? HL.at(d_hist_[hist_cur_].get()) : kNoHist;
-  P.acc_out = (float4*)(m + M.acc);
-  P.cnt_out = (uint32_t*)(m + M.cnt);
-  P.len_out = (uint32_t*)(m + M.len);
-  P.keep = keep ? HL.at(d_hist_[into].get()) : kNoHist;
-  hipStream_t s = lane0_ctx(false).stream;
-  k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
-  HIP_OK(hipGetLastError());
-  // the guides of this call, out of first_hit's buffer before its next user
-  HIP_OK(hipMemcpyAsync(m + M.t, fh + off[1], 4 * np, hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemcpyAsync(m + M.normal, fh + off[4], 12 * np, hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemcpyAsync(m + M.albedo, fh + off[5], 12 * np, hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemcpyAsync(m + M.kind, fh + off[6], np, hipMemcpyDeviceToDevice, s));
-  if (cnt) HIP_OK(hipMemcpyAsync(cnt, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
-  if (len) HIP_OK(hipMemcpyAsync(len, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
-  HIP_OK(download_rgb3(s, P.acc_out, np, acc3));
-  rp_merged_ = true;
-  rp_epoch_ = epoch_;
-  if (keep) {
-    hist_cur_ = into;
-    hist_epoch_ = epoch_;
-    memcpy(hist_cam_, cam_, sizeof hist_cam_);
-  }
-  return true;
+  const bool need_id = keep || ((flags & kRpSameShape) && history_state() != 0);
+  FhPlanes g;
+  if (!first_hit_launch(sample, kFhDir | kFhGuides | (need_id ? kFhId : 0u), g, err)) return false;
+  return post_.reproject(frame_ref(), g, RpTest{cos_min, eps_z, max_len, flags}, RpHostOut{acc3, cnt, len}, err);
 }
 
-bool Renderer::denoise_merged(uint32_t iterations, float sigma_c, float sigma_z, uint32_t flags, float* rgb3,
-                              uint8_t* valid, uint8_t* rgba, std::string& err) {
-  if (!rp_merged_ || !d_rp_) { err = "no merged frame"; return false; }
-  if (!rgb3 && !valid && !rgba) return true;
-  const size_t np = (size_t)w_ * h_;
-  HIP_OK(d_dn_.grow(dn_bytes(np)));
-  const RpMergedLayout M(np);
-  const char* m = d_rp_;
-  return dn_run(w_, h_, (const float4*)(m + M.acc), (const uint32_t*)(m + M.cnt), (const float*)(m + M.t),
-                (const float*)(m + M.normal), (const float*)(m + M.albedo), (const uint8_t*)(m + M.kind), d_dn_,
-                iterations, sigma_c, sigma_z, flags, rgb3, valid, rgba, err);
-}
-
-// ---------------------------------------------------------------------------
-// Guided upsampling (wpt_upsample.h)
-// ---------------------------------------------------------------------------
-
-namespace {
-// The outputs of a fine frame of nf pixels; every part 256 B aligned.
-struct UpLayout {
-  size_t rgb = 0, rgba = 0, valid = 0, bytes = 0;
-  constexpr explicit UpLayout(size_t nf) {
-    Slices z;
-    rgb = z.take(12 * nf); rgba = z.take(4 * nf); valid = z.take(nf);
-    bytes = z.at;
-  }
-};
-static_assert(UpLayout(1000).bytes == 17152 && UpLayout(1000).rgba == 12032 && UpLayout(1000).valid == 16128,
-              "upsample's layout");
-}  // namespace
-
-size_t Renderer::up_bytes(size_t nf) { return UpLayout(nf).bytes; }
-
-// k_upsample on lane 0's stream after the passes dn_passes queued there,
-// neither timed nor counted.
-bool Renderer::up_run(uint32_t W, uint32_t H, uint32_t scale, const char* dn_scratch, int cur, const float* hi_t,
-                      const float* hi_normal, const float* hi_albedo, const uint8_t* hi_kind, const float bg[3],
-                      float sigma_z, char* up_scratch, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
-  hipStream_t s = lane0_ctx(false).stream;
-  const DnLayout Z((size_t)W * H);
-  UpParams P;
-  P.A.W = W; P.A.H = H; P.A.s = scale;
-  P.A.sigma_z = sigma_z;
-  P.A.bg = mk(bg[0], bg[1], bg[2]);
-  P.fw = scale * W; P.fh = scale * H;
-  const size_t nf = (size_t)P.fw * P.fh;
-  const UpLayout U(nf);
-  P.rec.A = (const float4*)(dn_scratch + (cur ? Z.a1 : Z.a0));
-  P.rec.B = (const float4*)(dn_scratch + Z.b);
-  P.t = hi_t; P.normal = hi_normal; P.albedo = hi_albedo; P.kind = hi_kind;
-  P.rgb = rgb3 ? (float*)(up_scratch + U.rgb) : nullptr;
-  P.rgba = rgba ? (uint8_t*)(up_scratch + U.rgba) : nullptr;
-  P.valid = valid ? (uint8_t*)(up_scratch + U.valid) : nullptr;
-  const dim3 grid((P.fw + kDnTile - 1) / kDnTile, (P.fh + kDnTile - 1) / kDnTile);
-  k_upsample<<<grid, kBlock, 0, s>>>(P);
-  HIP_OK(hipGetLastError());
-  if (rgb3) HIP_OK(hipMemcpyAsync(rgb3, P.rgb, 12 * nf, hipMemcpyDeviceToHost, s));
-  if (valid) HIP_OK(hipMemcpyAsync(valid, P.valid, nf, hipMemcpyDeviceToHost, s));
-  if (rgba) HIP_OK(hipMemcpyAsync(rgba, P.rgba, 4 * nf, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return true;
-}
-
-// The session's frame as this rank holds it under k_first_hit's planes of
-// `sample`, or (kUpMerged) the merged frame and guides the last reproject left
-// in d_rp_; the fine guides are the scaled planes of `sample`. Everything stays
-// on the device; the frame, the counts, the rounds, the stock, the history, the
-// sample map and the counters are only read.
+// kUpMerged: the source is the merged frame and the guides the last reproject
+// left; the fine guides are the scaled planes of `sample` either way.
 bool Renderer::upsample(uint32_t scale, uint32_t sample, uint32_t iterations, float sigma_c, float sigma_z,
                         uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
   const bool merged = (flags & kUpMerged) != 0;
-  if (merged && (!rp_merged_ || !d_rp_)) { err = "no merged frame"; return false; }
+  if (merged && !has_merged()) { err = "no merged frame"; return false; }
   if (!rgb3 && !valid && !rgba) return true;
-  constexpr uint32_t kGuides = kFhT | kFhNormal | kFhAlbedo | kFhKind;
-  const size_t np = (size_t)w_ * h_, nf = (size_t)scale * w_ * ((size_t)scale * h_);
-  size_t off[7], hoff[7];
-  if (!merged && !first_hit_launch(sample, kGuides, off, err)) return false;
-  if (!first_hit_launch(sample, kGuides, hoff, err, scale)) return false;
-  HIP_OK(d_dn_.grow(dn_bytes(np)));
-  HIP_OK(d_up_.grow(up_bytes(nf)));
-  const RpMergedLayout M(np);
-  const char* fh = d_fh_;
-  const char* m = d_rp_;
-  const float4* acc = merged ? (const float4*)(m + M.acc) : d_acc_.get();
-  const uint32_t* cnt = merged ? (const uint32_t*)(m + M.cnt) : d_cnt_.get();
-  const float* t = (const float*)(merged ? m + M.t : fh + off[1]);
-  const float* normal = (const float*)(merged ? m + M.normal : fh + off[4]);
-  const float* albedo = (const float*)(merged ? m + M.albedo : fh + off[5]);
-  const uint8_t* kind = (const uint8_t*)(merged ? m + M.kind : fh + off[6]);
-  int cur = 0;
-  if (!dn_passes(w_, h_, acc, cnt, t, normal, albedo, kind, d_dn_, iterations, sigma_c, sigma_z, kDnAlbedo, cur, err))
-    return false;
-  const char* hi = d_fhs_;
-  return up_run(w_, h_, scale, d_dn_, cur, (const float*)(hi + hoff[1]), (const float*)(hi + hoff[4]),
-                (const float*)(hi + hoff[5]), (const uint8_t*)(hi + hoff[6]), ds_.bg, sigma_z, d_up_, rgb3, valid, rgba,
-                err);
+  FhPlanes lo, hi;
+  if (!merged && !first_hit_launch(sample, kFhGuides, lo, err)) return false;
+  if (!first_hit_launch(sample, kFhGuides, hi, err, scale)) return false;
+  return post_.upsample(frame_ref(), merged ? nullptr : &lo, scale, hi, DnParams{iterations, sigma_c, sigma_z, 0u},
+                        PostOut{rgb3, valid, rgba}, err);
 }
 
-bool Renderer::upsample_planes(uint32_t W, uint32_t H, uint32_t scale, const float* acc3, const uint32_t* cnt,
-                               const float* t, const float* normal3, const float* albedo3, const uint8_t* kind,
-                               const float* hi_t, const float* hi_normal3, const float* hi_albedo3,
-                               const uint8_t* hi_kind, const float* background3, uint32_t iterations, float sigma_c,
-                               float sigma_z, float* rgb3, uint8_t* valid, uint8_t* rgba, std::string& err) {
-  if (!stream_) { err = "no device"; return false; }
-  if (!rgb3 && !valid && !rgba) return true;
-  const size_t np = (size_t)W * H, nf = (size_t)scale * W * ((size_t)scale * H);
-  HookScratch S;
-  float4* d_acc = S.d<float4>(np);
-  uint32_t* d_cnt = S.d<uint32_t>(np);
-  float* d_t = S.d<float>(np);
-  float* d_n = S.d<float>(3 * np);
-  float* d_al = S.d<float>(3 * np);
-  uint8_t* d_kind = S.d<uint8_t>(np);
-  float* d_ht = S.d<float>(nf);
-  float* d_hn = S.d<float>(3 * nf);
-  float* d_hal = S.d<float>(3 * nf);
-  uint8_t* d_hkind = S.d<uint8_t>(nf);
-  char* dn_scratch = S.d<char>(dn_bytes(np));
-  char* up_scratch = S.d<char>(up_bytes(nf));
-  if (!S.ok) { err = "hipMalloc failed (upsample_planes)"; return false; }
-  std::vector<float4> a4;
-  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
-  HIP_OK(hipMemcpyAsync(d_cnt, cnt, sizeof(uint32_t) * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_t, t, sizeof(float) * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_al, albedo3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_ht, hi_t, sizeof(float) * nf, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_hn, hi_normal3, 12 * nf, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_hal, hi_albedo3, 12 * nf, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_hkind, hi_kind, nf, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  int cur = 0;
-  if (!dn_passes(W, H, d_acc, d_cnt, d_t, d_n, d_al, d_kind, dn_scratch, iterations, sigma_c, sigma_z, kDnAlbedo, cur,
-                 err))
-    return false;
-  return up_run(W, H, scale, dn_scratch, cur, d_ht, d_hn, d_hal, d_hkind, background3, sigma_z, up_scratch, rgb3, valid,
-                rgba, err);
-}
-
-// The history's planes are packed on the host with rp_pack, the function a
-// keeping k_reproject packs them with.
-bool Renderer::reproject_planes(uint32_t W, uint32_t H, const float* cam3, const float* acc3, const uint32_t* cnt,
-                                const float* dir3, const float* t, const int32_t* id, const float* normal3,
-                                const uint8_t* kind, const float* prev_cam5, const float* h_acc3,
-                                const uint32_t* h_cnt, const float* h_t, const int32_t* h_id, const float* h_normal3,
-                                const uint8_t* h_kind, float cos_min, float eps_z, uint32_t max_len, uint32_t flags,
-                                float* acc3_out, uint32_t* cnt_out, uint32_t* len_out, std::string& err) {
-  if (!stream_) { err = "no device"; return false; }
-  if (!acc3_out && !cnt_out && !len_out) return true;
-  const size_t np = (size_t)W * H;
-  const RpHistLayout HL(np);
-  HookScratch S;
-  float4* d_acc = S.d<float4>(2 * np);  // in, then out
-  uint32_t* d_cnt = S.d<uint32_t>(3 * np);  // in, out, len
-  float* d_dir = S.d<float>(3 * np);
-  float* d_t = S.d<float>(np);
-  int32_t* d_id = S.d<int32_t>(np);
-  float* d_n = S.d<float>(3 * np);
-  uint8_t* d_kind = S.d<uint8_t>(np);
-  char* d_h = S.d<char>(HL.bytes);
-  if (!S.ok) { err = "hipMalloc failed (reproject_planes)"; return false; }
-  std::vector<float4> a4;
-  std::vector<char> hb(HL.bytes, 0);
-  const RpHist hh = HL.at(hb.data());
-  for (size_t i = 0; i < np; i++) {
-    const RpKept k = rp_pack(mk(h_acc3[3 * i], h_acc3[3 * i + 1], h_acc3[3 * i + 2]), h_cnt[i]);
-    hh.k[i] = (uint32_t)h_kind[i] | (k.valid ? 0x100u : 0u);
-    hh.r0[i] = make_float4(k.c.x, k.c.y, k.c.z, u2f(h_cnt[i]));
-    hh.r1[i] = make_float4(h_normal3[3 * i], h_normal3[3 * i + 1], h_normal3[3 * i + 2], h_t[i]);
-    hh.id[i] = h_id[i];
+// The map reads k_first_hit's kinds of `sample` where the flags ask for them,
+// and the partition's membership where the frame has several ranks.
+bool Renderer::sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
+                          uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err) {
+  invalid = false;
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
+  FhPlanes g;
+  if ((flags & kMapMissOnce) && !first_hit_launch(sample, kFhKind, g, err)) return false;
+  std::vector<uint8_t> mb;
+  if (nranks_ > 1) {
+    mb.assign((size_t)w_ * h_, 0);
+    for (uint32_t p : part_pix_) mb[p] = 1;
   }
-  HIP_OK(upload_rgb3(stream_, acc3, np, a4, d_acc));
-  HIP_OK(hipMemcpyAsync(d_cnt, cnt, 4 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_dir, dir3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_t, t, 4 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_id, id, 4 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_n, normal3, 12 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_kind, kind, np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_h, hb.data(), HL.bytes, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  RpParams P;
-  P.A.W = W; P.A.H = H;
-  P.A.cam = mk(cam3[0], cam3[1], cam3[2]);
-  P.A.V = rp_view(W, H, prev_cam5);
-  P.A.cos_min = cos_min; P.A.eps_z = eps_z; P.A.max_len = max_len; P.A.flags = flags;
-  P.npix = (uint32_t)np;
-  P.acc = d_acc; P.cnt = d_cnt; P.dir = d_dir; P.t = d_t; P.id = d_id; P.normal = d_n; P.kind = d_kind;
-  P.hist = HL.at(d_h);
-  P.acc_out = d_acc + np; P.cnt_out = d_cnt + np; P.len_out = d_cnt + 2 * np;
-  P.keep = kNoHist;
-  hipStream_t s = lane0_ctx(false).stream;
-  k_reproject<<<blocks_for(np), kBlock, 0, s>>>(P);
-  HIP_OK(hipGetLastError());
-  if (cnt_out) HIP_OK(hipMemcpyAsync(cnt_out, P.cnt_out, 4 * np, hipMemcpyDeviceToHost, s));
-  if (len_out) HIP_OK(hipMemcpyAsync(len_out, P.len_out, 4 * np, hipMemcpyDeviceToHost, s));
-  HIP_OK(download_rgb3(s, P.acc_out, np, acc3_out));
-  return true;
+  return post_.sample_map(frame_ref(), g.kind, nranks_ > 1 ? &mb : nullptr, MapParams{target, max_pp, budget, flags},
+                          MapOut{count_out, total_out}, invalid, err);
 }
-
-// ---------------------------------------------------------------------------
-// Guided sampling (wpt_guided.h)
-// ---------------------------------------------------------------------------
 
 namespace {
-// sample_map's scratch for np pixels: the needs and their scan (np + 1 u64),
-// the chunk sums, the map itself and the membership plane
-struct MapLayout {
-  size_t pre = 0, sums = 0, count = 0, member = 0, bytes = 0;
-  uint32_t nb = 0;
-  constexpr explicit MapLayout(size_t np) {
-    nb = (uint32_t)((np + 1 + kScanChunk - 1) / kScanChunk);
-    Slices z;
-    pre = z.take(8 * (np + 1)); sums = z.take(8 * ((size_t)nb + 1)); count = z.take(4 * np); member = z.take(np);
-    bytes = z.at;
-  }
-};
 // compute_map's plan for a partition of npart of np pixels: the uploaded map,
 // the offsets (npart + 1) and bases, the scan's chunk sums, k_map_plan's words
 struct MapPlanLayout {
@@ -5930,112 +5491,10 @@ struct MapPlanLayout {
     bytes = z.at;
   }
 };
-// (scans in chunks of 1024: 5000 pixels are 5 chunks)
-static_assert(kScanChunk == 1024 && MapLayout(5000).nb == 5 && MapLayout(5000).bytes == 65792 &&
-                  MapLayout(5000).count == 40448 && MapLayout(5000).member == 60672,
-              "sample_map's layout");
 static_assert(MapPlanLayout(5000, 2500).nb == 3 && MapPlanLayout(5000, 2500).bytes == 41216 &&
                   MapPlanLayout(5000, 2500).sums == 40704 && MapPlanLayout(5000, 2500).words == 40960,
               "compute_map's layout");
 }  // namespace
-
-void Renderer::free_guided() {
-  d_map_.reset();
-  d_mplan_.reset();
-  map_ok_ = false;
-}
-
-// Needs, their scan, T back to the host, then the deal: on lane 0's stream like
-// the filter and the reprojection, neither timed nor counted.
-bool Renderer::map_run(uint32_t np, const uint32_t* cnt, const uint32_t* len, const uint8_t* kind,
-                       const uint8_t* member, char* scratch, uint32_t target, uint32_t max_pp, uint32_t budget,
-                       uint32_t flags, uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err) {
-  const MapLayout L(np);
-  u64* pre = (u64*)(scratch + L.pre);
-  u64* sums = (u64*)(scratch + L.sums);
-  uint32_t* count = (uint32_t*)(scratch + L.count);
-  const uint32_t n = np + 1;
-  hipStream_t s = lane0_ctx(false).stream;
-  k_map_need<<<blocks_for(n), kBlock, 0, s>>>(np, cnt, len, kind, member, target, max_pp, flags, pre);
-  k_scan64_local<<<L.nb, kBlock, 0, s>>>(pre, n, sums);
-  k_scan64_sums<<<1, kBlock, 0, s>>>(sums, L.nb);
-  k_scan64_add<<<L.nb, kBlock, 0, s>>>(pre, n, sums);
-  HIP_OK(hipGetLastError());
-  uint64_t T = 0;
-  HIP_OK(hipMemcpyAsync(&T, pre + np, sizeof T, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  if (total_out) { total_out[0] = T; total_out[1] = 0; }
-  if (T >= (1ull << 32)) {
-    invalid = true;
-    err = "sample_map: the needs sum to 2^32 or more (lower max_per_pixel)";
-    return false;
-  }
-  k_map_deal<<<blocks_for(np), kBlock, 0, s>>>(np, pre, budget, count);
-  HIP_OK(hipGetLastError());
-  if (count_out) HIP_OK(hipMemcpyAsync(count_out, count, 4 * (size_t)np, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  if (total_out) total_out[1] = map_dealt(budget, T);
-  return true;
-}
-
-// The session's map: its counts, the len plane the last reproject of this
-// accumulation left in d_rp_ (else 0 everywhere), k_first_hit's kinds of
-// `sample` where the flags read them, the partition's membership. The frame,
-// the rounds, the stock, the counters and the history are only read.
-bool Renderer::sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
-                          uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err) {
-  invalid = false;
-  if (!scene_ok_) { err = "no scene"; return false; }
-  if (w_ == 0 || h_ == 0 || !d_acc_) { err = "no viewport"; return false; }
-  const size_t np = (size_t)w_ * h_;
-  const uint8_t* kind = nullptr;
-  if (flags & kMapMissOnce) {
-    size_t off[7];
-    if (!first_hit_launch(sample, kFhKind, off, err)) return false;
-    kind = (const uint8_t*)(d_fh_ + off[6]);
-  }
-  const MapLayout L(np);
-  HIP_OK(d_map_.grow(L.bytes));
-  map_ok_ = false;
-  char* m = d_map_;
-  const uint8_t* member = nullptr;
-  if (nranks_ > 1) {
-    std::vector<uint8_t> mb(np, 0);
-    for (uint32_t p : part_pix_) mb[p] = 1;
-    HIP_OK(hipMemcpyAsync(m + L.member, mb.data(), np, hipMemcpyHostToDevice, stream_));
-    HIP_OK(hipStreamSynchronize(stream_));
-    member = (const uint8_t*)(m + L.member);
-  }
-  const uint32_t* len = nullptr;
-  if (rp_merged_ && d_rp_ && rp_epoch_ == epoch_) len = (const uint32_t*)(d_rp_ + RpMergedLayout(np).len);
-  if (!map_run((uint32_t)np, d_cnt_, len, kind, member, m, target, max_pp, budget, flags, count_out, total_out, invalid,
-               err))
-    return false;
-  map_ok_ = true;
-  map_epoch_ = epoch_;
-  return true;
-}
-
-bool Renderer::sample_map_planes(uint32_t W, uint32_t H, const uint32_t* cnt, const uint32_t* len,
-                                 const uint8_t* kind, const uint8_t* member, uint32_t target, uint32_t max_pp,
-                                 uint32_t budget, uint32_t flags, uint32_t* count_out, uint64_t* total_out,
-                                 bool& invalid, std::string& err) {
-  invalid = false;
-  if (!stream_) { err = "no device"; return false; }
-  const size_t np = (size_t)W * H;
-  HookScratch S;
-  uint32_t* d_cnt = S.d<uint32_t>(2 * np);  // cnt, len
-  uint8_t* d_km = S.d<uint8_t>(2 * np);     // kind, member
-  char* d_s = S.d<char>(MapLayout(np).bytes);
-  if (!S.ok) { err = "hipMalloc failed (sample_map_planes)"; return false; }
-  HIP_OK(hipMemcpyAsync(d_cnt, cnt, 4 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_cnt + np, len, 4 * np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_km, kind, np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipMemcpyAsync(d_km + np, member, np, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  return map_run((uint32_t)np, d_cnt, d_cnt + np, d_km, d_km + np, d_s, target, max_pp, budget, flags, count_out,
-                 total_out, invalid, err);
-}
 
 // Traces a sample map: partition entry p's pixel gets count[pixel] samples from
 // sample cnt[pixel] on. Every producer of samples leaves a pixel holding
@@ -6049,7 +5508,8 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
   invalid = false;
   if (!scene_ok_) { err = "no scene"; return false; }
   if (!d_acc_ || part_pix_.empty()) { err = "no viewport"; return false; }
-  if (!count && !(map_ok_ && d_map_ && map_epoch_ == epoch_)) {
+  const uint32_t* kept = count ? nullptr : post_.map_counts(epoch_, (size_t)w_ * h_);
+  if (!count && !kept) {
     invalid = true;
     err = "compute_map: no sample map of this accumulation on the device (wpt_sample_map)";
     return false;
@@ -6068,7 +5528,7 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
   u64* words = (u64*)(m + L.words);
   const uint32_t* src = (const uint32_t*)(m + L.in);
   if (count) HIP_OK(hipMemcpyAsync(m + L.in, count, 4 * np, hipMemcpyHostToDevice, stream_));
-  else src = (const uint32_t*)(d_map_ + MapLayout(np).count);
+  else src = kept;
   HIP_OK(hipMemsetAsync(words, 0, 2 * sizeof(u64), stream_));
   k_map_plan<<<blocks_for((uint64_t)npart + 1), kBlock, 0, stream_>>>(nranks_ > 1 ? d_part_pix_ : nullptr, npart, src,
                                                                      d_cnt_, off, base, words);

@@ -20,7 +20,7 @@
 // Two parts. The first is plain C++ for host and device: the projection, the
 // test and the sum of one tap, the merge, the pack of a kept pixel, and the
 // host restatement that calls them on planes. The second (WPT_REPROJECT_KERNELS,
-// wpt_render.hip) holds k_reproject, which calls the same functions on the
+// wpt_post.hip) holds k_reproject, which calls the same functions on the
 // history's records. Included inside namespace wpt, after wpt_denoise.h.
 //
 // A kept pixel is 40 bytes in four planes, so that a tap is one word and two

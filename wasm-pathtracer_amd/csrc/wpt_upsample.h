@@ -21,7 +21,7 @@
 // Two parts, like wpt_denoise.h, after which it is included inside namespace
 // wpt: plain C++ for host and device (the tap positions, one tap, one fine
 // pixel, the host restatement), then the kernel (WPT_UPSAMPLE_KERNELS,
-// wpt_render.hip), which calls the same functions.
+// wpt_post.hip), which calls the same functions.
 //
 // k_upsample: one lane per fine pixel, 16 x 16 fine tiles (k_dn_atrous's
 // geometry). A lane reads its fine guides (t, normal, albedo, kind: 29 B), and
