@@ -725,6 +725,49 @@ int wpt_sample_map_host(uint32_t W, uint32_t H, const uint32_t* cnt, const uint3
  * WPT_ERR_INVALID_ARG, with nothing traced: the partition's counts sum to more
  * than 2^32 - 1, or a pixel's cnt + count exceeds 2^32 - 1. */
 int wpt_compute_map(const uint32_t* count);
+/* Radiance along a caller's rays: a ray query is a camera path whose primary
+ * ray the caller supplies (light probes, irradiance at surface points, panorama,
+ * fisheye, orthographic or stereo cameras, a host that builds its own primary
+ * rays). Ray i = {ox,oy,oz,dx,dy,dz} as wpt_trace_rays takes them; its key k_i =
+ * keys[i], or i if keys is NULL; its samples are s = sample .. sample + spp - 1.
+ * The path of (i, s) has the xorshift32 stream path_seed(frame_seed, k_i, s)
+ * advanced by two draws (the two jitter draws of a camera ray, taken and
+ * discarded), throughput (1,1,1), origin and direction as given, and then
+ * trace_original_color's loop (src/tracer.rs) exactly as the session's
+ * batches run it for a camera path of render type `type` (WPT_NO_NEE,
+ * WPT_NORMAL_NEE, WPT_PNEE), under the session's scene, depth cap, frame seed
+ * and light-debug setting; WPT_PNEE builds or reuses the session's octree as
+ * wpt_compute does. The direction is used as given, not re-normalised: unit
+ * length is the caller's contract, and wpt_primary_rays' directions pass through
+ * bit for bit, so with rays6 = wpt_primary_rays(W, H, cam, seed, s), keys NULL
+ * and spp 1 the result is sample s of every pixel of a W x H frame of that
+ * render type, and the ray counts are that frame's.
+ *  rgb3    3 f32  ((+0 + c_0) + c_1) + ... over the ray's samples in sample
+ *                 order (RenderTarget::write's sum); the mean is the caller's
+ *                 division
+ *  status  u8     1 traced; 0 for a ray with a non-finite component or a
+ *                 direction of three zeros: not traced, rgb3 +0, no path and no
+ *                 ray counted. May be NULL.
+ * Ray i's result depends on (ray, key, sample, spp, type), the scene and the
+ * render options only: not on n, its position, the other rays, the batch size,
+ * the lane count, the partition (any rank answers any ray, no collective) or any
+ * wpt_set_option setting. The session is not touched: accumulation, counts,
+ * rounds and their positions, sample stock, sampling view, history, sample map
+ * and map mode stay as they are, and a wpt_compute after a query continues as if
+ * the query had not happened. The call first waits for the sample stock's
+ * refills in flight, as wpt_sync does; wpt_stats and wpt_kernel_times count its
+ * paths and rays as any batch's. flags: WPT_RAYS_DEVICE: rays6, keys, rgb3 and
+ * status are device pointers on the session's device (the call still returns
+ * synchronised). Inputs and outputs must not overlap. n == 0 succeeds, launches
+ * nothing and waits for nothing.
+ * WPT_ERR_INVALID_ARG, with nothing launched and nothing written: n > 0 with a
+ * null rays6 or rgb3, spp 0, type > 2, an unknown flag, sample + spp - 1 >
+ * 2^32 - 1, n >= 2^32. The definition to the operation: DESIGN.md §2. */
+#define WPT_RAYS_DEVICE 1u
+int wpt_radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                      uint32_t type, uint32_t flags, float* rgb3, uint8_t* status);
+/* Host only (no session, no GPU): the status rule above on n rays. */
+int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */

@@ -81,6 +81,8 @@ _SIGS = {
     "wpt_sample_map_planes": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
     "wpt_sample_map_host": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
     "wpt_compute_map": (ctypes.c_int, [c_p]),
+    "wpt_radiance_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
+    "wpt_rays_valid": (ctypes.c_int, [c_sz, c_p, c_p]),
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),

@@ -28,6 +28,7 @@ namespace {
 #include "wpt_reproject.h"  // likewise wpt_reproject_host's
 #include "wpt_guided.h"     // and wpt_sample_map_host's
 #include "wpt_upsample.h"   // and wpt_upsample_host's
+#include "wpt_rays.h"       // the validity rule of a query ray
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -1115,6 +1116,37 @@ int wpt_compute_map(const uint32_t* count) {
   bool invalid = false;
   if (!g_session->renderer.compute_map(count, invalid, err))
     return fail(invalid ? WPT_ERR_INVALID_ARG : WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+namespace {
+// the argument rules of wpt_radiance_rays
+const char* radiance_rays_args(size_t n, const float* rays6, uint32_t sample, uint32_t spp, uint32_t type,
+                               uint32_t flags, const float* rgb3) {
+  if (n && (!rays6 || !rgb3)) return "radiance_rays: null rays6 or rgb3";
+  if (spp == 0) return "radiance_rays: spp 0";
+  if (type > 2) return "radiance_rays: Invalid RenderType magic number";
+  if (flags & ~(uint32_t)WPT_RAYS_DEVICE) return "radiance_rays: unknown flag";
+  if ((uint64_t)sample + spp - 1 > 0xFFFFFFFFull) return "radiance_rays: a sample index would pass 2^32 - 1";
+  if ((uint64_t)n >= (1ull << 32)) return "radiance_rays: 2^32 rays or more";
+  return nullptr;
+}
+}  // namespace
+
+int wpt_radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
+                      uint32_t flags, float* rgb3, uint8_t* status) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  if (const char* e = radiance_rays_args(n, rays6, sample, spp, type, flags, rgb3)) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.radiance_rays(n, rays6, keys, sample, spp, type, (flags & WPT_RAYS_DEVICE) != 0, rgb3, status,
+                                         err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status) {
+  if (n && (!rays6 || !status)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  for (size_t i = 0; i < n; i++) status[i] = ray_valid(rays6 + 6 * i) ? 1 : 0;
   return WPT_OK;
 }
 

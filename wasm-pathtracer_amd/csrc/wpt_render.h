@@ -206,6 +206,17 @@ struct PathSet {
 // by piece, because an RR-only batch's launches depend on live counts read
 // back every finish_every bounces.
 constexpr int kAsyncLane0 = 2;
+// The ray source of a query batch (wpt_radiance_rays, wpt_rays.h): a chunk of
+// the caller's rays on the device. Position k of the chunk is ray k / spp,
+// sample `sample` + k % spp; the ray's sums are entry `ray` of acc / cnt.
+struct RayQuery {
+  const float* rays = nullptr;     // 6 f32 per ray {ox,oy,oz,dx,dy,dz}
+  const uint32_t* keys = nullptr;  // per ray, or null: key0 + ray
+  uint32_t key0 = 0;
+  uint32_t nrays = 0, spp = 1, sample = 0, type = 0;
+  float4* acc = nullptr;           // the query's own accumulation (k_accumulate_round's targets)
+  uint32_t* cnt = nullptr;
+};
 struct Batch {
   enum State { kNew, kBouncing, kCountWait, kIssued };
   // positions k0 .. k0+n-1 of: half h's current round (half >= 0), the
@@ -222,6 +233,9 @@ struct Batch {
   const uint32_t* mbase = nullptr;
   const uint32_t* mlist = nullptr;
   uint32_t nent = 0;
+  // a query batch: positions k0 .. k0+n-1 of the rays' chunk (batch_begin then
+  // picks k_generate_rays / k_generate_rays_ps, batch_tail the query's sums)
+  const RayQuery* rq = nullptr;
   bool stock = false;
   bool async = false;
   int queue = 0;      // async: 0 stock refills, 1 a random half's filler (each its own lanes, in order)
@@ -359,6 +373,15 @@ class Renderer {
   bool sample_map(uint32_t sample, uint32_t target, uint32_t max_pp, uint32_t budget, uint32_t flags,
                   uint32_t* count_out, uint64_t* total_out, bool& invalid, std::string& err);
   bool compute_map(const uint32_t* count, bool& invalid, std::string& err);
+  // Radiance along a caller's rays (wpt_rays.h, wpt_radiance_rays): camera paths
+  // of render type `type` whose primary rays are rays6, samples sample ..
+  // sample + spp - 1 on the streams of keys (null: the ray's index), summed per
+  // ray in sample order into rgb3; status (may be null) 0 for a ray not traced.
+  // device: the four are device pointers. The batches are run_batch's with the
+  // rays as their source; the frame, the rounds, the stock and the map are not
+  // touched. The caller checks the arguments.
+  bool radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
+                     bool device, float* rgb3, uint8_t* status, std::string& err);
   // WPT_OPT_MAP_MODE: a map was traced in this accumulation (wpt_compute is an
   // error until the next reset)
   bool map_mode() const { return map_mode_; }
@@ -732,6 +755,11 @@ class Renderer {
   // the partition). map_mode_: reset() clears it.
   DevBuf<char> d_mplan_;
   bool map_mode_ = false;
+  // radiance_rays' scratch of one chunk of rays (sums, counts; for host pointers
+  // also rays, keys, rgb, status) and its pinned staging block; freed with the
+  // lanes
+  DevBuf<char> d_query_;
+  PinBuf<char> h_query_;
   bool compute_end(std::string& err);  // what every tracing call ends with: counts, overflow flag, work counters
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];

@@ -2570,6 +2570,9 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 #define WPT_GUIDED_PLAN_KERNEL
 #include "wpt_guided.h"
 #include "wpt_upsample.h"
+// the query generators (last, so that the functions above keep their order)
+#define WPT_RAYS_KERNELS
+#include "wpt_rays.h"
 
 }  // namespace
 
@@ -2770,6 +2773,8 @@ void Renderer::free_lane_paths(PathSet& L) {
 
 void Renderer::free_paths() {
   for (PathSet& L : lanes_) free_lane_paths(L);
+  d_query_.reset();
+  h_query_.reset();
 }
 
 bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
@@ -3452,11 +3457,12 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
   // RR-only batches (the k_finish hand-over reads one live count per lane)
   // run without the presolve
   B.presolve = presolve_ && max_depth_ > 0 && num_guards_ != 0;
-  B.pnee = left_type_ == 2 || right_type_ == 2;
+  // (a query batch's paths all have the call's render type)
+  B.pnee = B.rq ? B.rq->type == 2u : left_type_ == 2 || right_type_ == 2;
   // k_generate_shade shades the primary rays it resolves (WPT_OPT_GEN_SHADE);
   // PNEE batches (k_shade stages the octree) and stock batches (the count
-  // word) keep k_generate_ps.
-  const bool gen_shade = gen_shade_ && B.presolve && !B.pnee && !B.stock;
+  // word) keep k_generate_ps; query batches have generators of their own.
+  const bool gen_shade = gen_shade_ && B.presolve && !B.pnee && !B.stock && !B.rq;
   const ShadeParams SP = shade_params();
   if (profiling_ && !B.async) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
@@ -3478,7 +3484,18 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
     const uint32_t nn = (uint32_t)C.paths;
     // (the presolved counts, the words from kResWord on, only where they are used)
     HIP_OK(hipMemsetAsync(L.counts, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), s));
-    if (gen_shade) {
+    if (B.rq) {
+      // the caller's rays as bounce 0 (wpt_rays.h)
+      if (B.presolve)
+        LAUNCH_TIMED(C, 0, generate, n_generate,
+                     k_generate_rays_ps<<<blocks_for(nn), kBlock, 0, s>>>(
+                         *B.rq, seed_, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, ds_,
+                         L.t, L.id, reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop_miss_ ? 1u : 0u));
+      else
+        LAUNCH_TIMED(C, 0, generate, n_generate,
+                     k_generate_rays<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, B.k0 + B.off[i], nn, L.pixel,
+                                                                     L.thr[0], L.col, L.ro[0], L.rd[0], L.counts));
+    } else if (gen_shade) {
       // a persistent grid, as k_shade's: the variant's own occupancy
       const int ti = ds_.tri_only ? 1 : 0;
       if (gen_shade_occ_[ti] == 0) {
@@ -3694,9 +3711,13 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
   }
   // a sample round, or an explicit mapping that is not a stock batch (a sample
   // map, compute_map): a pixel's paths are consecutive, L.pixel its entry
-  const bool round = B.half >= 0 || B.moff;
+  // A query batch likewise: a ray's paths are consecutive, L.pixel the ray, the
+  // targets the query's own sums (no partition list: any rank answers any ray).
+  const bool round = B.half >= 0 || B.moff || B.rq;
   const uint32_t npix = B.part ? B.npix : (uint32_t)part_pix_.size();
-  const uint32_t* part = B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
+  const uint32_t* part = B.rq ? nullptr : B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
+  float4* const acc = B.rq ? B.rq->acc : d_acc_.get();
+  uint32_t* const cnt = B.rq ? B.rq->cnt : d_cnt_.get();
   // in-order accumulation: lane i's slice after lane i-1's (each pixel's
   // samples are summed in sample order, as RenderTarget::write does); a
   // stock batch stores each path into its ring slot instead
@@ -3711,7 +3732,7 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
       k_stock_store<<<blocks_for(nn), kBlock, 0, s>>>(L.pixel, nn, L.col, d_stock_);
     else if (round)
       LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
-                   k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, d_acc_, d_cnt_));
+                   k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, acc, cnt));
     else
       LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
                    k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, s>>>(
@@ -4280,6 +4301,7 @@ bool Renderer::run_batch(uint64_t k0, uint64_t n, int half, std::string& err, co
     B.mlist = map->mlist;
     B.nent = map->nent;
     B.stock = map->stock;
+    B.rq = map->rq;  // or a query's rays
   }
   // the batch is cut into contiguous slices, one per lane (small batches: one
   // lane); each slice is a sub-range of the path (or round-position) sequence
@@ -4315,7 +4337,15 @@ bool Renderer::run_batch(uint64_t k0, uint64_t n, int half, std::string& err, co
     times_.logical[5] += B.fused ? (uint64_t)(b - 1) : 0u;
   }
   stats_.bounces += (uint64_t)b;
-  if (!B.stock) stats_.paths += n;  // a stock batch's samples count when a round takes them
+  if (B.rq) {
+    // a query's paths are its valid rays': bounce 0's rays, streamed, resolved or dropped (the counts just flushed)
+    for (int l = 0; l < B.nl; l++) {
+      const uint32_t* hc = lanes_[l].h_counts;
+      stats_.paths += (uint64_t)hc[0] + (B.presolve ? (uint64_t)hc[kResWord] + hc[kResWord + 1] : 0u);
+    }
+  } else if (!B.stock) {
+    stats_.paths += n;  // a stock batch's samples count when a round takes them
+  }
   if (log_) WPT_LOGF("batch done n=%lu bounces=%d finished=%d\n", (unsigned long)n, b, B.finished ? 1 : 0);
   return true;
 }
@@ -5560,6 +5590,111 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
   const uint64_t cap = std::max<uint64_t>(std::min(batch_cap(), bsz), 1);
   for (uint64_t k0 = 0; k0 < total; k0 += cap)
     if (!run_batch(k0, std::min<uint64_t>(cap, total - k0), -1, err, nullptr, 0, &M)) return false;
+  return compute_end(err);
+}
+
+// Radiance along a caller's rays (wpt_rays.h): the rays go through in chunks of
+// at most kQueryChunk, each a call of its own (a ray's result depends on no
+// other ray). A chunk's scratch: the float4 sums and counts k_accumulate_round
+// adds to (lane after lane, so a ray's samples may straddle lanes and batches),
+// and for host pointers the rays, keys, rgb and status with one pinned staging
+// block. The batch loop is compute_map's; rounds_, map_mode_, epoch_ and
+// next_path_ are not touched, the frame is not read.
+namespace {
+constexpr size_t kQueryChunk = (size_t)1 << 21;  // a 1080p frame's rays are one chunk
+struct QueryLayout {
+  size_t acc, cnt, sums_end, rays, keys, rgb, status, bytes;
+  constexpr QueryLayout(size_t n, bool host, bool keyed)
+      : acc(0), cnt(0), sums_end(0), rays(0), keys(0), rgb(0), status(0), bytes(0) {
+    Slices s;
+    acc = s.take(sizeof(float4) * n);
+    cnt = s.take(sizeof(uint32_t) * n);
+    sums_end = s.at;
+    if (host) {
+      rays = s.take(6 * sizeof(float) * n);
+      keys = s.take(keyed ? sizeof(uint32_t) * n : 0);
+      rgb = s.take(3 * sizeof(float) * n);
+      status = s.take(n);
+    }
+    bytes = s.at;
+  }
+};
+}  // namespace
+
+bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                             uint32_t type, bool device, float* rgb3, uint8_t* status, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (n == 0) return true;
+  // refills and fill batches in flight use the lanes this call may resize
+  if (!sync(err)) return false;
+  if (type == 2u && !build_photons(err)) return false;
+  const uint64_t bsz = std::min<uint64_t>(std::max<uint64_t>(batch_, 1), 0xFFFFFFFFull);
+  for (size_t c0 = 0; c0 < n; c0 += kQueryChunk) {
+    const size_t cn = std::min(kQueryChunk, n - c0);
+    const uint32_t cnn = (uint32_t)cn;
+    const QueryLayout Q(cn, !device, keys != nullptr);
+    HIP_OK(d_query_.grow(Q.bytes));
+    char* m = d_query_;
+    RayQuery R;
+    R.acc = (float4*)(m + Q.acc);
+    R.cnt = (uint32_t*)(m + Q.cnt);
+    float* d_rgb = rgb3 + 3 * c0;
+    uint8_t* d_status = status ? status + c0 : nullptr;
+    char* hp = nullptr;
+    if (device) {
+      R.rays = rays6 + 6 * c0;
+      R.keys = keys ? keys + c0 : nullptr;
+    } else {
+      // the staging block mirrors the device block's host part
+      HIP_OK(h_query_.grow(Q.bytes));
+      hp = h_query_;
+      memcpy(hp + Q.rays, rays6 + 6 * c0, 6 * sizeof(float) * cn);
+      if (keys) memcpy(hp + Q.keys, keys + c0, sizeof(uint32_t) * cn);
+      // rays and keys lie next to each other: one copy up (rgb and status likewise: one copy back)
+      const size_t up = (keys ? Q.keys + sizeof(uint32_t) * cn : Q.rays + 6 * sizeof(float) * cn) - Q.rays;
+      HIP_OK(hipMemcpyAsync(m + Q.rays, hp + Q.rays, up, hipMemcpyHostToDevice, stream_));
+      R.rays = (const float*)(m + Q.rays);
+      R.keys = keys ? (const uint32_t*)(m + Q.keys) : nullptr;
+      d_rgb = (float*)(m + Q.rgb);
+      d_status = (uint8_t*)(m + Q.status);
+    }
+    R.key0 = (uint32_t)c0;
+    R.nrays = cnn;
+    R.spp = spp;
+    R.sample = sample;
+    R.type = type;
+    HIP_OK(hipMemsetAsync(m, 0, Q.sums_end, stream_));  // the sums and counts
+    if (status) {
+      k_rays_status<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.rays, d_status);
+      HIP_OK(hipGetLastError());
+    }
+    const uint64_t total = (uint64_t)cn * spp;
+    {
+      // the lanes' capacity, as compute() sizes it
+      const int ml = main_lanes();
+      const uint64_t want = std::min(bsz, total);
+      const uint64_t per = (want + ml - 1) / ml;
+      for (int i = 0; i < ml; i++)
+        if (!ensure_lane(i, (i == 0 && want < (uint64_t)ml * kMinLanePaths) ? want : per, err)) return false;
+    }
+    Batch M;
+    M.rq = &R;
+    const uint64_t cap = std::max<uint64_t>(std::min(batch_cap(), bsz), 1);
+    for (uint64_t k0 = 0; k0 < total; k0 += cap)
+      if (!run_batch(k0, std::min<uint64_t>(cap, total - k0), -1, err, nullptr, 0, &M)) return false;
+    // (the main stream has waited for every lane's accumulation: batch_tail)
+    k_rays_unpack<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.acc, d_rgb);
+    HIP_OK(hipGetLastError());
+    if (!device) {
+      const size_t back = (status ? Q.status + cn : Q.rgb + 3 * sizeof(float) * cn) - Q.rgb;
+      HIP_OK(hipMemcpyAsync(hp + Q.rgb, m + Q.rgb, back, hipMemcpyDeviceToHost, stream_));
+    }
+    HIP_OK(hipStreamSynchronize(stream_));
+    if (!device) {
+      memcpy(rgb3 + 3 * c0, hp + Q.rgb, 3 * sizeof(float) * cn);
+      if (status) memcpy(status + c0, hp + Q.status, cn);
+    }
+  }
   return compute_end(err);
 }
 

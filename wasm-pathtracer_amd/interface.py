@@ -462,6 +462,55 @@ def primary_rays(width, height, cam, seed=0xBABABEBE, sample=0):
     return rays
 
 
+RAYS_DEVICE = 1  # WPT_RAYS_DEVICE: radiance_rays' arrays are device pointers
+
+
+def radiance_rays(rays, keys=None, sample=0, spp=1, type=1, device=False):
+    """Path-traced radiance along a caller's rays (wpt_radiance_rays): ray i =
+    rays[i] = {origin, direction}, its samples sample .. sample + spp - 1 on
+    the streams of keys[i] (None: i), as camera paths of render type `type`
+    under the session's scene and render options. Returns (rgb (n, 3) f32: the
+    sum over the ray's samples in sample order, status (n,) u8: 0 for a ray
+    with a non-finite component or a zero direction, which is not traced).
+    device=True: rays (n, 6) f32 and keys (n,) i32 / u32 bits are contiguous
+    torch tensors on the session's device, and so are the results (status as
+    torch.uint8); the call still returns synchronised. The session's frame,
+    rounds, stock and map are not touched."""
+    if device:
+        import torch
+
+        if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 6:
+            raise ValueError("rays: a contiguous float32 tensor of 6 components per ray")
+        n = rays.numel() // 6
+        if keys is not None and (keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 or not keys.is_contiguous()
+                                 or keys.numel() != n or keys.device != rays.device):
+            raise ValueError("keys: a contiguous 32-bit integer tensor of one key per ray, on the rays' device")
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        _check(lib().wpt_radiance_rays(n, rays.data_ptr(), keys.data_ptr() if keys is not None else None, sample, spp,
+                                       type, RAYS_DEVICE, rgb.data_ptr(), status.data_ptr()))
+        return rgb, status
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+    rgb = np.empty((n, 3), dtype=np.float32)
+    status = np.empty(n, dtype=np.uint8)
+    _check(lib().wpt_radiance_rays(n, r.ctypes.data, None if k is None else k.ctypes.data, sample, spp, type, 0,
+                                   rgb.ctypes.data, status.ctypes.data))
+    return rgb, status
+
+
+def rays_valid(rays):
+    """The status radiance_rays gives each ray (wpt_rays_valid; host only, no
+    session): 1 if its six components are finite and its direction is not three
+    zeros."""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    status = np.empty(r.shape[0], dtype=np.uint8)
+    _check(lib().wpt_rays_valid(r.shape[0], r.ctypes.data, status.ctypes.data))
+    return status
+
+
 DENOISE_ALBEDO = 1  # WPT_DENOISE_ALBEDO: filter radiance / albedo on diffuse hits, multiply the albedo back
 # the documented defaults of denoise(): see profiles/denoise/README.md
 DENOISE_DEFAULTS = {"iterations": 3, "sigma_c": 1.0, "sigma_z": 0.1, "flags": DENOISE_ALBEDO}
