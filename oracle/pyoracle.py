@@ -32,6 +32,8 @@ def lib():
         L.oracle_shadow_rays.argtypes = [c_p, c_sz, c_p, c_p, c_p]
         L.oracle_render.argtypes = [c_p, c_u32, c_u32, c_p, c_int, c_int, c_int, c_u32, c_u32, c_u32, c_u32, c_u32,
                                     c_u32, c_u32, c_u32, c_int, c_p, c_p, c_int]
+        L.oracle_radiance_rays.argtypes = [c_p, c_sz, c_p, c_p, c_u32, c_u32, c_int, c_int, c_u32, c_int, c_int, c_p, c_p,
+                                           c_p]
         L.oracle_reference_compute.argtypes = [c_p, c_u32, c_u32, c_p, c_int, c_int, c_int, c_p, c_sz, c_p, c_p, c_p]
         L.oracle_bvh4.restype = c_sz
         L.oracle_bvh4.argtypes = [c_p, c_p]
@@ -129,6 +131,25 @@ class OracleScene:
         lib().oracle_render(self.h, width, height, c.ctypes.data, left_type, right_type, max_depth, seed, s0, spp, x0,
                             y0, x1, y1, row_step, threads, acc.ctypes.data, st.ctypes.data, int(light_debug))
         return acc, {"rays": int(st[0]), "shadow_rays": int(st[1]), "node_visits": int(st[2])}
+
+    def radiance_rays(self, rays, keys=None, sample=0, spp=1, type=1, max_depth=0, seed=0xBABABEBE, light_debug=0,
+                      threads=1):
+        """The ray query (wpt_radiance_rays) on the oracle: ray i on
+        the streams path_seed(seed, keys[i] or i, sample + k), k < spp, two draws
+        discarded, the direction as given; PNEE uses this scene's photon tree as
+        render() does. Returns (rgb (n, 3) f32: the f32 sum in sample order,
+        status (n,) u8: 0 for a ray that is not traced, stats dict)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+        assert spp >= 1 and sample + spp - 1 <= 0xFFFFFFFF and n < (1 << 32) and type in (0, 1, 2)
+        rgb = np.empty((n, 3), dtype=np.float32)
+        status = np.empty(n, dtype=np.uint8)
+        st = np.zeros(3, dtype=np.uint64)
+        lib().oracle_radiance_rays(self.h, n, r.ctypes.data, None if k is None else k.ctypes.data, sample, spp, type,
+                                   max_depth, seed, int(light_debug), threads, rgb.ctypes.data, status.ctypes.data,
+                                   st.ctypes.data)
+        return rgb, status, {"rays": int(st[0]), "shadow_rays": int(st[1]), "node_visits": int(st[2])}
 
     def reference_compute(self, width, height, cam, num_samples, left_type=1, right_type=1, max_depth=0,
                           rng_state=0xBABABEBE, acc=None, cnt=None):

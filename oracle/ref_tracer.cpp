@@ -495,6 +495,69 @@ void oracle_render(void* p, uint32_t W, uint32_t H, const float* cam, int left_t
   }
 }
 
+// Ray query (include/wpt.h wpt_radiance_rays, DESIGN §2 "Radiance along a
+// caller's rays"; build-defined, the reference traces camera rays only): ray i
+// = rays6[6 i ..] = {origin, direction}, key k_i = keys[i] (or i, 32-bit), and
+// for k in 0 .. spp - 1 the path on the stream path_seed(frame_seed, k_i,
+// sample + k) advanced by two draws (a camera ray's jitter, discarded), the
+// direction as given. rgb3[i] = ((+0 + c_0) + c_1) + ... in f32. A ray with a
+// non-finite component or a direction of three zeros (either sign): status 0,
+// rgb +0, nothing traced or counted. The rule is restated here on the values.
+// Threads take rays in turn; a ray's result and counts depend on the ray alone.
+// status may be NULL. stats = {rays, shadow_rays, node_visits}.
+void oracle_radiance_rays(void* p, size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                          int type, int max_depth, uint32_t frame_seed, int light_debug, int threads, float* rgb3,
+                          uint8_t* status, uint64_t* stats) {
+  const Scene& s = ((OracleHandle*)p)->scene;
+  const bool dbg = light_debug != 0;
+  if (threads < 1) threads = 1;
+  PhotonTree* photons = type == PNEE && !s.lights.empty() ? ((OracleHandle*)p)->photon_tree(frame_seed, threads) : nullptr;
+  std::vector<PathStats> st(threads);
+  std::atomic<size_t> next(0);
+  const size_t grain = 16;
+  auto work = [&](int tid) {
+    for (;;) {
+      const size_t i0 = next.fetch_add(grain);
+      if (i0 >= n) break;
+      for (size_t i = i0; i < std::min(n, i0 + grain); i++) {
+        const float* r = rays6 + 6 * i;
+        bool ok = true;
+        for (int c = 0; c < 6; c++) ok = ok && std::isfinite(r[c]);
+        // a zero of either sign; a denormal is not one (classified, not compared: no flush mode changes it)
+        ok = ok && !(std::fpclassify(r[3]) == FP_ZERO && std::fpclassify(r[4]) == FP_ZERO && std::fpclassify(r[5]) == FP_ZERO);
+        float* out = rgb3 + 3 * i;
+        out[0] = out[1] = out[2] = 0.0f;
+        if (status) status[i] = ok ? 1 : 0;
+        if (!ok) continue;
+        const uint32_t key = keys ? keys[i] : (uint32_t)i;
+        const Ray ray = make_ray(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+        for (uint32_t k = 0; k < spp; k++) {
+          Rng rng;
+          rng.state = path_seed(frame_seed, key, sample + k);
+          rng.next();
+          rng.next();
+          Vec3 col = trace_original_color(s, ray, rng, (RenderType)type, dbg, max_depth, st[tid], photons);
+          out[0] += col.x;
+          out[1] += col.y;
+          out[2] += col.z;
+        }
+      }
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < threads; t++) pool.emplace_back(work, t);
+  work(0);
+  for (auto& th : pool) th.join();
+  if (stats) {
+    stats[0] = stats[1] = stats[2] = 0;
+    for (auto& x : st) {
+      stats[0] += x.rays;
+      stats[1] += x.shadow_rays;
+      stats[2] += x.node_visits;
+    }
+  }
+}
+
 // Reference execution model (mode A): ONE sequential xorshift32
 // stream (rng.rs:11) shared by pixel selection and paths, RandomSamplingStrategy
 // (sampling_strategy.rs:56-59) on each viewport half, `compute(n)` splitting

@@ -99,11 +99,13 @@ def test_frames_produce_their_conditions(wpt, oracle):
 
 def test_keys_select_the_stream(wpt, oracle):
     """What makes two rays of equal geometry and different keys differ somewhere
-    in the GPU test's list. The oracle traces camera rays only, so it cannot
-    hold the geometry and change the key; what it can say: the streams of the
-    keys the GPU test uses (0 .. 256, and those shifted by 1000) all differ,
-    and a box path's value depends on its stream (every diffuse hit draws from
-    it): the same pixels on another sample's streams give another frame."""
+    in tests/test_gpu_rays.py's list: the streams of the keys it uses (0 .. 256,
+    and those shifted by 1000) all differ, and a box path's value depends on its
+    stream (every diffuse hit draws from it): the same pixels on another
+    sample's streams give another frame. The oracle's own ray query holds the
+    geometry and changes the key directly: tests/test_rays_oracle_cpu.py::test_keys
+    (one ray under 300 keys gives more than 100 distinct answers), and
+    tests/test_gpu_rays_adversarial.py compares the device's keyed answers with it."""
     L = oracle.lib()
     seeds = {L.oracle_path_seed(rf.SEED, k, 0) for k in list(range(257)) + list(range(1000, 1257))}
     assert len(seeds) == 514
