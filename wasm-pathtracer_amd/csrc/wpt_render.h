@@ -262,13 +262,48 @@ struct LaunchCtx {
   bool async = false;            // the launch belongs to an async batch ...
   uint64_t paths = 0;            // ... of this many paths in the lane's slice
   int batch_lanes = 1;           // lanes of the batch (1: full-capacity traversal grids)
-  bool timed = false;            // LAUNCH_TIMED: the main lanes' launches when profiling
+  bool timed = false;            // launch_timed: the main lanes' launches when profiling
   bool count = false;            // the kernels' work-counting variants
   int bounce = 0;
   int hit_sel = 0;               // the hit-record buffers a traversal launch writes (bounce & 1 when presolving)
   // the presolved count of the bounce's stream (probing: added to the
   // launch's record, see k_probe_add), or null
   const uint32_t* probe_res = nullptr;
+};
+
+// The numbering of the kernel variants: what a launcher computes from named
+// run-time flags, the index into the family's table of instantiations
+// (wpt_render.hip, "Kernel variant tables", where each is checked against its
+// table) and into the renderer's per-variant grid and occupancy caches.
+// k_extend, k_shadow (trav: 0 exact BVH2, 1 BVH4 fast path):
+constexpr int trav_variant(bool tri_only, bool count, int trav) {
+  return (tri_only ? 1 : 0) | (count ? 2 : 0) | (trav << 2);
+}
+constexpr int trace_variant(bool tri_only, bool count) { return (tri_only ? 1 : 0) | (count ? 2 : 0); }
+// k_shade (oct: the PNEE octree's LDS view, 0 without PNEE; cr: the paths
+// write their ray counts; ps: the kernel presolves)
+constexpr int shade_variant(bool tri_only, bool pnee, int oct, bool cr, bool ps) {
+  return (ps ? 16 : 0) + (cr ? 8 : 0) + (tri_only ? 4 : 0) + (pnee ? 1 + oct : 0);
+}
+constexpr int finish_variant(bool tri_only, bool pnee, bool cr) {
+  return (tri_only ? 1 : 0) | (pnee ? 2 : 0) | (cr ? 4 : 0);
+}
+// k_generate_shade, k_first_hit, k_photon_hit
+constexpr int scene_variant(bool tri_only) { return tri_only ? 1 : 0; }
+// k_photon_sample: the octree view itself
+constexpr int oct_variant(int view) { return view; }
+constexpr int kTravVariants = trav_variant(true, true, 1) + 1;
+constexpr int kTraceVariants = trace_variant(true, true) + 1;
+constexpr int kShadeVariants = shade_variant(true, true, 2, true, true) + 1;
+constexpr int kFinishVariants = finish_variant(true, true, true) + 1;
+constexpr int kSceneVariants = scene_variant(true) + 1;
+constexpr int kOctVariants = oct_variant(2) + 1;
+
+// A kernel's resident blocks per CU at one dynamic LDS size, queried on first
+// use and again when the size changes (blocks 0: not yet queried).
+struct OccCache {
+  uint32_t blocks = 0;
+  size_t smem = 0;
 };
 
 class Renderer {
@@ -504,6 +539,16 @@ class Renderer {
   bool exchange_frame(std::string& err);
   bool plan_slice(int h, uint64_t a, uint64_t b, uint64_t& local, std::string& err);
   void free_rounds();
+  // The launchers: each takes its kernel's variant from the session's and the
+  // batch's state (wpt_render.hip, "Kernel variant tables") and launches it in
+  // context C. launch_timed runs `launch` (one kernel launch) and, when C is
+  // timed, records its interval for timing slot `slot` (resolve_timings).
+  template <class F>
+  bool launch_timed(const LaunchCtx& C, int slot, F&& launch, std::string& err);
+  bool launch_generate(const Batch& B, int i, std::string& err);  // bounce 0 of slice i
+  bool launch_shade(const Batch& B, const LaunchCtx& C, std::string& err);
+  // the live paths of C's lane after bounce C.bounce, to their end (g blocks)
+  bool launch_finish(const Batch& B, const LaunchCtx& C, uint32_t g, std::string& err);
   bool launch_extend(const LaunchCtx& C, const float4* ro, const float4* rd, const uint32_t* cnt, std::string& err);
   bool launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* occ_out, std::string& err);
   bool launch_trace(const LaunchCtx& C, std::string& err);
@@ -689,16 +734,14 @@ class Renderer {
 
   int device_ = -1;
   int ncu_ = 256;
-  // persistent grids per kernel variant (tri_only + 2 count + 4 traversal):
-  // [0..7] multi-lane batches (grid_pct_ of the resident capacity), [8..15]
-  // one-lane batches (all of it); k_trace: tri_only + 2 count
-  static constexpr int kTravVariants = 8;
+  // persistent grids per kernel variant (trav_variant): [v] multi-lane
+  // batches (grid_pct_ of the resident capacity), [kTravVariants + v]
+  // one-lane batches (all of it); k_trace: trace_variant
   uint32_t grid_ext_[2 * kTravVariants] = {};
   uint32_t grid_sh_[2 * kTravVariants] = {};
-  uint32_t grid_tr_[4] = {};
+  uint32_t grid_tr_[kTraceVariants] = {};
   uint32_t grid_shade_ = 512;      // k_shade blocks (kShadeBlock lanes each) resident on the chip (the least occupied variant)
-  uint32_t shade_occ_[32] = {};  // per k_shade variant (x ray counting): resident blocks per CU (0: not yet queried)
-  size_t shade_occ_smem_[32] = {};  // ... for this dynamic LDS size
+  OccCache shade_occ_[kShadeVariants];  // per shade_variant
   bool fused_ = false;             // WPT_OPT_FUSED: bounce b's extension + bounce b-1's shadow rays in one k_trace for every batch
   // batches below this many paths (adaptive sample rounds) always run fused:
   // one launch per bounce drains one pool of rays instead of two (WPT_OPT_FUSED_BELOW)
@@ -724,7 +767,7 @@ class Renderer {
   bool drop_miss_ = true;          // WPT_OPT_DROP_MISS: a ray resolved to a miss that adds nothing is not written to the next stream
   bool presolve_shadow_ = true;    // WPT_OPT_PRESOLVE_SHADOW: k_shade adds the contribution of a shadow ray it resolves unoccluded
   bool gen_shade_ = true;          // WPT_OPT_GEN_SHADE: k_generate_shade shades the primary rays it resolves (bounce 0 of them in no stream)
-  uint32_t gen_shade_occ_[2] = {};  // k_generate_shade<TRI_ONLY>: resident blocks per CU (0: not yet queried)
+  OccCache gen_shade_occ_[kSceneVariants];  // k_generate_shade, per scene_variant
   // WPT_OPT_PROBE: wave timelines of the next probe_cap_ traversal launches
   // (probe_read); meta per launch {kernel, lane, bounce, waves, first entry}
   uint32_t probe_cap_ = 0, probe_waves_ = 0, probe_used_ = 0;

@@ -17,6 +17,7 @@
 #include "wpt_seqsum.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdlib>
 #include <cmath>
@@ -28,6 +29,7 @@
 #include <unordered_map>
 #include <thread>
 #include <type_traits>
+#include <utility>
 
 // WPT_OPT_LOG lines, stamped with the host's monotonic clock in ms (Python's
 // time.monotonic() on Linux: tools/session_rate.py marks its calls with it)
@@ -2574,6 +2576,138 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 #define WPT_RAYS_KERNELS
 #include "wpt_rays.h"
 
+// ===========================================================================
+// Kernel variant tables
+// ===========================================================================
+// One table per templated kernel family: entry V is the instantiation whose
+// template arguments At<V> decodes from V, and At<V>::index encodes the same
+// arguments again with the family's index function (wpt_render.h), the one the
+// launchers call with run-time flags. The static_asserts hold the two together
+// for every entry: table[index(flags...)] is kernel<flags...>. Below this
+// section no kernel of these families is named with literal arguments.
+// The entries are named from the last to the first, so the compiler
+// instantiates them in that order and the device code lists a kernel's plain
+// variant (index 0 of its flags) after the others, as it always has: what
+// reads the listing by a name fragment (tests/test_build_occupancy.py) keeps
+// finding that one.
+template <template <size_t> class At, size_t... V>
+constexpr auto variant_table(std::index_sequence<V...>) {
+  constexpr size_t N = sizeof...(V);
+  const std::array down{At<N - 1 - V>::fn...};
+  std::array up = down;
+  for (size_t v = 0; v < N; v++) up[v] = down[N - 1 - v];
+  return up;
+}
+template <template <size_t> class At, size_t... V>
+constexpr bool variant_table_ok(std::index_sequence<V...>) {
+  constexpr auto table = variant_table<At>(std::index_sequence<V...>{});
+  return ((At<V>::index == (int)V && table[At<V>::index] == At<V>::fn) && ...);
+}
+template <int N>
+using Variants = std::make_index_sequence<N>;
+
+template <size_t V>
+struct ExtendAt {
+  static constexpr bool T = V & 1, CN = V & 2;
+  static constexpr int F = V >> 2;
+  static constexpr auto fn = &k_extend<T, CN, F>;
+  static constexpr int index = trav_variant(T, CN, F);
+};
+template <size_t V>
+struct ShadowAt : ExtendAt<V> {
+  static constexpr auto fn = &k_shadow<ExtendAt<V>::T, ExtendAt<V>::CN, ExtendAt<V>::F>;
+};
+template <size_t V>
+struct TraceAt {
+  static constexpr bool T = V & 1, CN = V & 2;
+  static constexpr auto fn = &k_trace<T, CN>;
+  static constexpr int index = trace_variant(T, CN);
+};
+// (TRI_ONLY, CR, PS) x the four (PNEE, OCT) pairs: NEE, and PNEE with the
+// octree in global memory (0) or in LDS (1 the child array, 2 and the CDFs)
+template <size_t V>
+struct ShadeAt {
+  static constexpr bool T = V & 4, PN = V & 3, CR = V & 8, PS = V & 16;
+  static constexpr int OC = PN ? (V & 3) - 1 : 0;
+  static constexpr auto fn = &k_shade<T, PN, OC, CR, PS>;
+  static constexpr int index = shade_variant(T, PN, OC, CR, PS);
+};
+template <size_t V>
+struct FinishAt {
+  static constexpr bool T = V & 1, PN = V & 2, CR = V & 4;
+  static constexpr auto fn = &k_finish<T, PN, CR>;
+  static constexpr int index = finish_variant(T, PN, CR);
+};
+template <size_t V>
+struct GenShadeAt {
+  static constexpr auto fn = &k_generate_shade<V != 0>;
+  static constexpr int index = scene_variant(V != 0);
+};
+template <size_t V>
+struct FirstHitAt {
+  static constexpr auto fn = &k_first_hit<V != 0>;
+  static constexpr int index = scene_variant(V != 0);
+};
+template <size_t V>
+struct PhotonHitAt {
+  static constexpr auto fn = &k_photon_hit<V != 0>;
+  static constexpr int index = scene_variant(V != 0);
+};
+template <size_t V>
+struct PhotonSampleAt {
+  static constexpr auto fn = &k_photon_sample<(int)V>;
+  static constexpr int index = oct_variant((int)V);
+};
+
+constexpr auto kExtendTable = variant_table<ExtendAt>(Variants<kTravVariants>{});
+constexpr auto kShadowTable = variant_table<ShadowAt>(Variants<kTravVariants>{});
+constexpr auto kTraceTable = variant_table<TraceAt>(Variants<kTraceVariants>{});
+constexpr auto kShadeTable = variant_table<ShadeAt>(Variants<kShadeVariants>{});
+constexpr auto kFinishTable = variant_table<FinishAt>(Variants<kFinishVariants>{});
+constexpr auto kGenShadeTable = variant_table<GenShadeAt>(Variants<kSceneVariants>{});
+constexpr auto kFirstHitTable = variant_table<FirstHitAt>(Variants<kSceneVariants>{});
+constexpr auto kPhotonHitTable = variant_table<PhotonHitAt>(Variants<kSceneVariants>{});
+constexpr auto kPhotonSampleTable = variant_table<PhotonSampleAt>(Variants<kOctVariants>{});
+
+static_assert(variant_table_ok<ExtendAt>(Variants<kTravVariants>{}), "k_extend's table");
+static_assert(variant_table_ok<ShadowAt>(Variants<kTravVariants>{}), "k_shadow's table");
+static_assert(variant_table_ok<TraceAt>(Variants<kTraceVariants>{}), "k_trace's table");
+static_assert(variant_table_ok<ShadeAt>(Variants<kShadeVariants>{}), "k_shade's table");
+static_assert(variant_table_ok<FinishAt>(Variants<kFinishVariants>{}), "k_finish's table");
+static_assert(variant_table_ok<GenShadeAt>(Variants<kSceneVariants>{}), "k_generate_shade's table");
+static_assert(variant_table_ok<FirstHitAt>(Variants<kSceneVariants>{}), "k_first_hit's table");
+static_assert(variant_table_ok<PhotonHitAt>(Variants<kSceneVariants>{}), "k_photon_hit's table");
+static_assert(variant_table_ok<PhotonSampleAt>(Variants<kOctVariants>{}), "k_photon_sample's table");
+// spot checks in plain words: one entry per family, named by its flags
+static_assert(kExtendTable[trav_variant(true, false, 1)] == &k_extend<true, false, 1> &&
+                  kShadowTable[trav_variant(false, true, 0)] == &k_shadow<false, true, 0> &&
+                  kTraceTable[trace_variant(false, true)] == &k_trace<false, true> &&
+                  kShadeTable[shade_variant(true, true, 2, false, true)] == &k_shade<true, true, 2, false, true> &&
+                  kShadeTable[shade_variant(false, false, 0, true, false)] == &k_shade<false, false, 0, true, false> &&
+                  kFinishTable[finish_variant(false, true, true)] == &k_finish<false, true, true> &&
+                  kGenShadeTable[scene_variant(true)] == &k_generate_shade<true> &&
+                  kFirstHitTable[scene_variant(false)] == &k_first_hit<false> &&
+                  kPhotonHitTable[scene_variant(true)] == &k_photon_hit<true> &&
+                  kPhotonSampleTable[oct_variant(1)] == &k_photon_sample<1>,
+              "the tables' numbering");
+
+// Resident blocks per CU (at least 1) of `kernel` in blocks of `block` threads
+// with `smem` bytes of dynamic LDS.
+template <class K>
+bool occupancy(K kernel, uint32_t block, size_t smem, uint32_t& blocks, std::string& err) {
+  int bpc = 0;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, (int)block, smem));
+  blocks = (uint32_t)std::max(bpc, 1);
+  return true;
+}
+// The same through a variant's cache.
+template <class K>
+bool cached_occupancy(OccCache& c, K kernel, uint32_t block, size_t smem, std::string& err) {
+  if (c.blocks != 0 && c.smem == smem) return true;
+  c.smem = smem;
+  return occupancy(kernel, block, smem, c.blocks, err);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -3292,21 +3426,23 @@ bool Renderer::ensure_lane(int i, uint64_t n, std::string& err) {
 
 bool Renderer::ensure_paths(uint64_t n, std::string& err) { return ensure_lane(0, n, err); }
 
-// A launch of context C (its `timed` and `stream`), its interval recorded.
-#define LAUNCH_TIMED(C, slot, accum, counter, ...)                       \
-  do {                                                                   \
-    hipEvent_t a_ = nullptr, b_ = nullptr;                               \
-    if ((C).timed) {                                                     \
-      if (!next_event(&a_, err) || !next_event(&b_, err)) return false;  \
-      HIP_OK(hipEventRecord(a_, (C).stream));                            \
-    }                                                                    \
-    __VA_ARGS__;                                                         \
-    HIP_OK(hipGetLastError());                                           \
-    if ((C).timed) {                                                     \
-      HIP_OK(hipEventRecord(b_, (C).stream));                            \
-      pending_.push_back(PendingTiming{a_, b_, slot});                   \
-    }                                                                    \
-  } while (0)
+// A launch of context C (its `timed` and `stream`), its interval recorded for
+// timing slot `slot` (the order of KernelTimes' members).
+template <class F>
+bool Renderer::launch_timed(const LaunchCtx& C, int slot, F&& launch, std::string& err) {
+  hipEvent_t a = nullptr, b = nullptr;
+  if (C.timed) {
+    if (!next_event(&a, err) || !next_event(&b, err)) return false;
+    HIP_OK(hipEventRecord(a, C.stream));
+  }
+  launch();
+  HIP_OK(hipGetLastError());
+  if (C.timed) {
+    HIP_OK(hipEventRecord(b, C.stream));
+    pending_.push_back(PendingTiming{a, b, slot});
+  }
+  return true;
+}
 
 bool Renderer::next_event(hipEvent_t* e, std::string& err) {
   if (ev_used_ == ev_pool_.size()) {
@@ -3443,27 +3579,12 @@ auto Renderer::gen_params(uint32_t npix, uint32_t scale) const {
 // Lanes, slices and bounce 0 of batch B (k_generate on each lane's stream,
 // after the main stream's work so far: reset, round planning, k_spec_plan).
 bool Renderer::batch_begin(Batch& B, std::string& err) {
-  // the mapping: an explicit one (stock batches), half h's current round,
-  // or paths k0 .. k0+n-1 of the sequence path k -> (pixel list[k % npix],
-  // sample k / npix) over this rank's pixels or over `part` (a screen half)
-  const bool round = B.half >= 0 && !B.moff;
-  const uint32_t* rnd_off = B.moff ? B.moff : round ? rounds_[B.half].rc : nullptr;
-  const uint32_t* rnd_base = B.moff ? B.mbase : round ? rounds_[B.half].rbase : nullptr;
-  const uint32_t npix = B.moff ? B.nent : B.part ? B.npix : (uint32_t)part_pix_.size();
-  const uint32_t* part = B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
-  const GenParams G = gen_params(npix);
-  const uint32_t slots = B.stock ? stock_used_slots_ : 0u;
   for (int i = 0; i <= B.nl; i++) B.off[i] = B.n * (uint64_t)i / (uint64_t)B.nl;
   // RR-only batches (the k_finish hand-over reads one live count per lane)
   // run without the presolve
   B.presolve = presolve_ && max_depth_ > 0 && num_guards_ != 0;
   // (a query batch's paths all have the call's render type)
   B.pnee = B.rq ? B.rq->type == 2u : left_type_ == 2 || right_type_ == 2;
-  // k_generate_shade shades the primary rays it resolves (WPT_OPT_GEN_SHADE);
-  // PNEE batches (k_shade stages the octree) and stock batches (the count
-  // word) keep k_generate_ps; query batches have generators of their own.
-  const bool gen_shade = gen_shade_ && B.presolve && !B.pnee && !B.stock && !B.rq;
-  const ShadeParams SP = shade_params();
   if (profiling_ && !B.async) HIP_OK(hipEventRecord(ev_ref_, stream_));
   HIP_OK(hipEventRecord(ev_main_, stream_));
   for (int i = 0; i < B.nl; i++) {
@@ -3481,53 +3602,9 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
     if (l != 0) HIP_OK(hipStreamWaitEvent(s, ev_main_, 0));  // after reset / round planning on the main stream
     // a low-priority stream after the lane's last main batch (its buffers)
     if (s != L.stream) HIP_OK(hipStreamWaitEvent(s, L.done, 0));
-    const uint32_t nn = (uint32_t)C.paths;
     // (the presolved counts, the words from kResWord on, only where they are used)
     HIP_OK(hipMemsetAsync(L.counts, 0, sizeof(uint32_t) * (B.presolve ? kCountWords : kResWord), s));
-    if (B.rq) {
-      // the caller's rays as bounce 0 (wpt_rays.h)
-      if (B.presolve)
-        LAUNCH_TIMED(C, 0, generate, n_generate,
-                     k_generate_rays_ps<<<blocks_for(nn), kBlock, 0, s>>>(
-                         *B.rq, seed_, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, ds_,
-                         L.t, L.id, reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop_miss_ ? 1u : 0u));
-      else
-        LAUNCH_TIMED(C, 0, generate, n_generate,
-                     k_generate_rays<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, B.k0 + B.off[i], nn, L.pixel,
-                                                                     L.thr[0], L.col, L.ro[0], L.rd[0], L.counts));
-    } else if (gen_shade) {
-      // a persistent grid, as k_shade's: the variant's own occupancy
-      const int ti = ds_.tri_only ? 1 : 0;
-      if (gen_shade_occ_[ti] == 0) {
-        int bpc = 0;
-        if (ti) HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_generate_shade<true>, (int)kShadeBlock, 0));
-        else HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_generate_shade<false>, (int)kShadeBlock, 0));
-        gen_shade_occ_[ti] = (uint32_t)std::max(bpc, 1);
-      }
-      const uint32_t tiles = std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock);
-      const uint32_t gg = WPT_GEN_SHADE_ONESHOT || (C.async && async_oneshot_)
-                              ? tiles
-                              : std::min<uint32_t>(tiles, (uint32_t)ncu_ * gen_shade_occ_[ti]);
-      const RayStream s0{L.ro[0], L.rd[0], L.thr[0]};
-      const RayStream s1{L.ro[1], L.rd[1], L.thr[1]};
-      const ShadowStream sh{L.so, L.sd, L.sc};
-#define WPT_GENSH(T)                                                                                                 \
-  k_generate_shade<T><<<gg, kShadeBlock, 0, s>>>(G, part, B.k0 + B.off[i], nn, L.pixel, L.col, rnd_off, rnd_base, \
-                                                 B.mlist, ds_, SP, s0, s1, sh, L.hit_t(1), L.hit_id(1), L.counts)
-      if (ti) LAUNCH_TIMED(C, 0, generate, n_generate, WPT_GENSH(true));
-      else LAUNCH_TIMED(C, 0, generate, n_generate, WPT_GENSH(false));
-#undef WPT_GENSH
-    } else if (B.presolve)
-      LAUNCH_TIMED(C, 0, generate, n_generate,
-                   k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, s>>>(
-                       G, part, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, rnd_off,
-                       rnd_base, B.mlist, slots, ds_, L.t, L.id, reinterpret_cast<uint32_t*>(L.res_ctr(0)),
-                       drop_miss_ ? 1u : 0u));
-    else
-      LAUNCH_TIMED(C, 0, generate, n_generate,
-                   k_generate<<<blocks_for(nn), kBlock, 0, s>>>(G, part, B.k0 + B.off[i], nn, L.pixel, L.thr[0], L.col,
-                                                              L.ro[0], L.rd[0], L.counts, rnd_off, rnd_base, B.mlist,
-                                                              slots));
+    if (!launch_generate(B, i, err)) return false;
   }
   B.maxb = max_depth_ > 0 ? std::min(max_depth_, kMaxBounces) : kMaxBounces;
   // fused: bounce b >= 1 traces its extension rays together with bounce b-1's
@@ -3544,28 +3621,6 @@ bool Renderer::batch_begin(Batch& B, std::string& err) {
 // of an RR-only batch must come back first. block: wait for such counts;
 // else return with B in kCountWait when they have not landed yet.
 bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
-  const ShadeParams SP = shade_params();
-  // the paths of C's lane in stream rin, to their end, one lane each
-  auto launch_finish = [&](const LaunchCtx& C, const RayStream& rin, uint32_t g, bool pn) -> bool {
-    const PathSet& L = *C.ps;
-#define WPT_FIN(T, PN, CR)                                                                                 \
-  k_finish<T, PN, CR><<<g, kTBlock, 0, C.stream>>>(ds_, SP, rin, L.ext_count(C.bounce + 1), L.col, L.spill, \
-                                                  L.counts + kFinishWord)
-#define WPT_FIN2(T, PN) \
-  if (B.stock) WPT_FIN(T, PN, true); \
-  else WPT_FIN(T, PN, false)
-    if (ds_.tri_only) {
-      if (pn) WPT_FIN2(true, true);
-      else WPT_FIN2(true, false);
-    } else {
-      if (pn) WPT_FIN2(false, true);
-      else WPT_FIN2(false, false);
-    }
-#undef WPT_FIN2
-#undef WPT_FIN
-    HIP_OK(hipGetLastError());
-    return true;
-  };
   while (B.state == Batch::kBouncing || B.state == Batch::kCountWait) {
     if (B.state == Batch::kCountWait) {
       // the live counts of bounce b = B.b - 1 (RR-only batches): stop once
@@ -3602,12 +3657,10 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
           // next bounce): they are the paths' next colour additions
           if (B.fused && !launch_shadow(C, L.sh_count(b), nullptr, err)) return false;
           if (live[i] == 0) continue;
-          const RayStream rin{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
-          const uint32_t g =
-              (uint32_t)std::min<uint64_t>((live[i] + kTBlock - 1) / kTBlock,
-                                           std::min(async_grid(C, grid_tr_[ds_.tri_only ? 1 : 0], trace_grid_pct_),
-                                                    spill_grid(L)));
-          if (!launch_finish(C, rin, g, B.pnee)) return false;
+          const uint32_t g = (uint32_t)std::min<uint64_t>(
+              (live[i] + kTBlock - 1) / kTBlock,
+              std::min(async_grid(C, grid_tr_[trace_variant(ds_.tri_only, false)], trace_grid_pct_), spill_grid(L)));
+          if (!launch_finish(B, C, g, err)) return false;
         }
         B.finished = true;
         break;
@@ -3619,69 +3672,9 @@ bool Renderer::batch_advance(Batch& B, bool block, std::string& err) {
     for (int i = 0; i < B.nl; i++) {
       const LaunchCtx C = batch_ctx(B, i, b);
       const PathSet& L = *C.ps;
-      const uint32_t nn = (uint32_t)C.paths;
-      const int hs = C.hit_sel;
       const bool traced = (B.fused && b > 0) ? launch_trace(C, err)
                                              : launch_extend(C, L.ro[b & 1], L.rd[b & 1], L.ext_count(b), err);
-      if (!traced) return false;
-      {
-        const RayStream in{L.ro[b & 1], L.rd[b & 1], L.thr[b & 1]};
-        const RayStream out{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
-        const ShadowStream sh{L.so, L.sd, L.sc};
-        [[maybe_unused]] const uint32_t sgrid =
-            std::max<uint32_t>(1, std::min<uint32_t>((nn + kShadeBlock - 1) / kShadeBlock, grid_shade_));
-        // the persistent grid of the variant launched: its own occupancy
-        // (VGPRs, and the octree's LDS for OC), cached per variant and LDS size
-#if WPT_SHADE_GRID_VAR
-#define WPT_SHADE_GRID(T, PN, OC, CR, PS)                                                                       \
-  const int vi = (PS ? 16 : 0) + (CR ? 8 : 0) + (T ? 4 : 0) + (PN ? 1 + OC : 0);                                \
-  const size_t smem = OC ? 4 * (size_t)ds_.oct_lds_words : 0;                                                   \
-  if (shade_occ_[vi] == 0 || shade_occ_smem_[vi] != smem) {                                                     \
-    int bpc = 0;                                                                                                \
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_shade<T, PN, OC, CR, PS>, (int)kShadeBlock, smem)); \
-    shade_occ_[vi] = (uint32_t)std::max(bpc, 1);                                                                \
-    shade_occ_smem_[vi] = smem;                                                                                 \
-  }                                                                                                             \
-  const uint32_t sg = std::max<uint32_t>(1, std::min<uint32_t>((nn + kShadeBlock - 1) / kShadeBlock,            \
-                                                               (uint32_t)ncu_ * shade_occ_[vi]));
-#else
-#define WPT_SHADE_GRID(T, PN, OC, CR, PS) const uint32_t sg = sgrid;
-#endif
-#define WPT_SHADE1(T, PN, OC, CR, PS)                                                                               \
-  do {                                                                                                              \
-    WPT_SHADE_GRID(T, PN, OC, CR, PS)                                                                               \
-    const uint32_t sgo = C.async && async_oneshot_ ? std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock) : sg; \
-    LAUNCH_TIMED(C, 2, shade, n_shade,                                                                              \
-                 k_shade<T, PN, OC, CR, PS><<<sgo, kShadeBlock, OC ? 4 * ds_.oct_lds_words : 0, C.stream>>>(        \
-                     ds_, SP, in, out, sh, L.col, L.ext_count(b), L.hit_t(hs), L.hit_id(hs), L.append_ctr(b),      \
-                     L.hit_t(hs ^ 1), L.hit_id(hs ^ 1), nn));                                                       \
-  } while (0)
-// a stock batch's paths write their ray counts (CR)
-#define WPT_SHADE(T, PN, OC)              \
-  do {                                    \
-    if (B.presolve) {                                \
-      if (B.stock) WPT_SHADE1(T, PN, OC, true, true);    \
-      else WPT_SHADE1(T, PN, OC, false, true);           \
-    } else if (B.stock) WPT_SHADE1(T, PN, OC, true, false); \
-    else WPT_SHADE1(T, PN, OC, false, false);            \
-  } while (0)
-        // PNEE: the octree from LDS when oct_lds_words covers it (child array and CDFs, or the child array)
-        const int oc = !B.pnee || ds_.oct_lds_words == 0 ? 0 : (ds_.oct_lds_words > ds_.oct_nodes ? 2 : 1);
-        if (ds_.tri_only) {
-          if (!B.pnee) WPT_SHADE(true, false, 0);
-          else if (oc == 2) WPT_SHADE(true, true, 2);
-          else if (oc == 1) WPT_SHADE(true, true, 1);
-          else WPT_SHADE(true, true, 0);
-        } else {
-          if (!B.pnee) WPT_SHADE(false, false, 0);
-          else if (oc == 2) WPT_SHADE(false, true, 2);
-          else if (oc == 1) WPT_SHADE(false, true, 1);
-          else WPT_SHADE(false, true, 0);
-        }
-#undef WPT_SHADE
-#undef WPT_SHADE1
-#undef WPT_SHADE_GRID
-      }
+      if (!traced || !launch_shade(B, C, err)) return false;
       if (!B.fused && !launch_shadow(C, L.sh_count(b), nullptr, err)) return false;
     }
     B.b = b + 1;
@@ -3730,13 +3723,14 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
     if (i > 0 && !B.stock) HIP_OK(hipStreamWaitEvent(s, B.async ? B.done[i - 1] : lanes_[l - 1].done, 0));
     if (B.stock)
       k_stock_store<<<blocks_for(nn), kBlock, 0, s>>>(L.pixel, nn, L.col, d_stock_);
-    else if (round)
-      LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
-                   k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, acc, cnt));
-    else
-      LAUNCH_TIMED(C, 4, accumulate, n_accumulate,
-                   k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, s>>>(
-                       part, B.k0 + B.off[i], nn, npix, L.col, d_acc_, d_cnt_));
+    else if (!launch_timed(C, 4, [&] {
+               if (round)
+                 k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, acc, cnt);
+               else
+                 k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, s>>>(
+                     part, B.k0 + B.off[i], nn, npix, L.col, d_acc_, d_cnt_);
+             }, err))
+      return false;
     HIP_OK(hipGetLastError());
     // ray statistics from the per-bounce counts (done: after this copy too)
     uint32_t* hc = B.async ? B.hc + (size_t)i * kCountWords : L.h_counts;
@@ -4561,31 +4555,129 @@ bool Renderer::copy_partition(float* dev_dst, std::string& err) {
   return true;
 }
 
+// Bounce 0 of slice i of batch B on its lane: a query batch's own rays
+// (wpt_rays.h), or the primary rays of B's mapping.
+bool Renderer::launch_generate(const Batch& B, int i, std::string& err) {
+  const LaunchCtx C = batch_ctx(B, i, 0);
+  const PathSet& L = *C.ps;
+  const hipStream_t s = C.stream;
+  const uint32_t nn = (uint32_t)C.paths;
+  const uint64_t k0 = B.k0 + B.off[i];
+  const uint32_t drop = drop_miss_ ? 1u : 0u;
+  if (B.rq) {
+    const auto launch = [&] {
+      if (B.presolve)
+        k_generate_rays_ps<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
+                                                            L.rd[0], L.counts, ds_, L.t, L.id,
+                                                            reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop);
+      else
+        k_generate_rays<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
+                                                         L.rd[0], L.counts);
+    };
+    return launch_timed(C, 0, launch, err);
+  }
+  // the mapping: an explicit one (stock batches), half h's current round,
+  // or paths k0 .. k0+n-1 of the sequence path k -> (pixel list[k % npix],
+  // sample k / npix) over this rank's pixels or over `part` (a screen half)
+  const bool round = B.half >= 0 && !B.moff;
+  const uint32_t* rnd_off = B.moff ? B.moff : round ? rounds_[B.half].rc : nullptr;
+  const uint32_t* rnd_base = B.moff ? B.mbase : round ? rounds_[B.half].rbase : nullptr;
+  const uint32_t npix = B.moff ? B.nent : B.part ? B.npix : (uint32_t)part_pix_.size();
+  const uint32_t* part = B.part ? B.part : (nranks_ > 1 ? d_part_pix_ : nullptr);
+  const GenParams G = gen_params(npix);
+  const uint32_t slots = B.stock ? stock_used_slots_ : 0u;
+  // k_generate_shade shades the primary rays it resolves (WPT_OPT_GEN_SHADE);
+  // PNEE batches (k_shade stages the octree) and stock batches (the count
+  // word) keep k_generate_ps.
+  if (gen_shade_ && B.presolve && !B.pnee && !B.stock) {
+    // a persistent grid, as k_shade's: the variant's own occupancy
+    const int v = scene_variant(ds_.tri_only);
+    if (!cached_occupancy(gen_shade_occ_[v], kGenShadeTable[v], kShadeBlock, 0, err)) return false;
+    const uint32_t tiles = std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock);
+    const uint32_t g = WPT_GEN_SHADE_ONESHOT || (C.async && async_oneshot_)
+                           ? tiles
+                           : std::min<uint32_t>(tiles, (uint32_t)ncu_ * gen_shade_occ_[v].blocks);
+    const RayStream s0{L.ro[0], L.rd[0], L.thr[0]};
+    const RayStream s1{L.ro[1], L.rd[1], L.thr[1]};
+    const ShadowStream sh{L.so, L.sd, L.sc};
+    const auto launch = [&] {
+      kGenShadeTable[v]<<<g, kShadeBlock, 0, s>>>(G, part, k0, nn, L.pixel, L.col, rnd_off, rnd_base, B.mlist, ds_,
+                                                 shade_params(), s0, s1, sh, L.hit_t(1), L.hit_id(1), L.counts);
+    };
+    return launch_timed(C, 0, launch, err);
+  }
+  const auto launch = [&] {
+    if (B.presolve)
+      k_generate_ps<<<(nn + kBlock * kGenTile - 1u) / (kBlock * kGenTile), kBlock, 0, s>>>(
+          G, part, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0], L.counts, rnd_off, rnd_base, B.mlist, slots, ds_,
+          L.t, L.id, reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop);
+    else
+      k_generate<<<blocks_for(nn), kBlock, 0, s>>>(G, part, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0], L.rd[0],
+                                                  L.counts, rnd_off, rnd_base, B.mlist, slots);
+  };
+  return launch_timed(C, 0, launch, err);
+}
+
+// Bounce C.bounce's hits of C's lane shaded: the next bounce's extension rays
+// and this bounce's shadow rays, in a persistent grid.
+bool Renderer::launch_shade(const Batch& B, const LaunchCtx& C, std::string& err) {
+  const PathSet& L = *C.ps;
+  const int b = C.bounce, hs = C.hit_sel;
+  const uint32_t nn = (uint32_t)C.paths;
+  // PNEE: the octree from LDS when oct_lds_words covers it (child array and CDFs, or the child array)
+  const int oc = !B.pnee || ds_.oct_lds_words == 0 ? 0 : (ds_.oct_lds_words > ds_.oct_nodes ? 2 : 1);
+  // (a stock batch's paths write their ray counts: CR)
+  const int v = shade_variant(ds_.tri_only, B.pnee, oc, B.stock, B.presolve);
+  const size_t smem = oc ? 4 * (size_t)ds_.oct_lds_words : 0;
+  const uint32_t tiles = std::max<uint32_t>(1, (nn + kShadeBlock - 1) / kShadeBlock);
+#if WPT_SHADE_GRID_VAR
+  // the resident blocks of the variant launched: its own occupancy (VGPRs,
+  // and the octree's LDS), cached per variant and LDS size
+  if (!cached_occupancy(shade_occ_[v], kShadeTable[v], kShadeBlock, smem, err)) return false;
+  const uint32_t resident = (uint32_t)ncu_ * shade_occ_[v].blocks;
+#else
+  const uint32_t resident = grid_shade_;
+#endif
+  const uint32_t g = C.async && async_oneshot_ ? tiles : std::min(tiles, resident);
+  const RayStream in{L.ro[b & 1], L.rd[b & 1], L.thr[b & 1]};
+  const RayStream out{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
+  const ShadowStream sh{L.so, L.sd, L.sc};
+  const auto launch = [&] {
+    kShadeTable[v]<<<g, kShadeBlock, smem, C.stream>>>(ds_, shade_params(), in, out, sh, L.col, L.ext_count(b),
+                                                      L.hit_t(hs), L.hit_id(hs), L.append_ctr(b), L.hit_t(hs ^ 1),
+                                                      L.hit_id(hs ^ 1), nn);
+  };
+  return launch_timed(C, 2, launch, err);
+}
+
+// The live paths of C's lane after bounce C.bounce (an RR-only batch's), each
+// run to its end, in a grid of g blocks.
+bool Renderer::launch_finish(const Batch& B, const LaunchCtx& C, uint32_t g, std::string& err) {
+  const PathSet& L = *C.ps;
+  const int b = C.bounce;
+  const RayStream rin{L.ro[(b + 1) & 1], L.rd[(b + 1) & 1], L.thr[(b + 1) & 1]};
+  kFinishTable[finish_variant(ds_.tri_only, B.pnee, B.stock)]<<<g, kTBlock, 0, C.stream>>>(
+      ds_, shade_params(), rin, L.ext_count(b + 1), L.col, L.spill, L.counts + kFinishWord);
+  HIP_OK(hipGetLastError());
+  return true;
+}
+
 // Launch one bounce of the extend kernel over rays (ro, rd) 0..*cnt-1 with
 // the scene's traversal (trav_ext_: 0 exact BVH2, 1 BVH4 fast path). Hits go
 // to the hit records C.hit_sel of C's lane.
 bool Renderer::launch_extend(const LaunchCtx& C, const float4* ro, const float4* rd, const uint32_t* cnt,
                              std::string& err) {
   const PathSet& L = *C.ps;
-  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0) | (trav_ext_ << 2);
+  const int v = trav_variant(ds_.tri_only, C.count, trav_ext_);
   const int full = C.batch_lanes == 1 ? kTravVariants : 0;
   const uint32_t g = std::min(async_grid(C, grid_ext_[v + full], 100), spill_grid(L));
   DevScene ds = ds_;
   ds.probe = probe_slot(C, 1, g);
-#define WPT_EXT(T, CN, F)                                                                                     \
-  k_extend<T, CN, F><<<g, kTBlock, 0, C.stream>>>(ds, ro, rd, cnt, L.hit_t(C.hit_sel), L.hit_id(C.hit_sel), \
-                                                 L.spill, d_work_, d_fallback_)
-  switch (v) {
-    case 0: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, false, 0)); break;
-    case 1: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, false, 0)); break;
-    case 2: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, true, 0)); break;
-    case 3: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, true, 0)); break;
-    case 4: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, false, 1)); break;
-    case 5: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, false, 1)); break;
-    case 6: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(false, true, 1)); break;
-    default: LAUNCH_TIMED(C, 1, extend, n_extend, WPT_EXT(true, true, 1)); break;
-  }
-#undef WPT_EXT
+  const auto launch = [&] {
+    kExtendTable[v]<<<g, kTBlock, 0, C.stream>>>(ds, ro, rd, cnt, L.hit_t(C.hit_sel), L.hit_id(C.hit_sel), L.spill,
+                                                d_work_, d_fallback_);
+  };
+  if (!launch_timed(C, 1, launch, err)) return false;
   if (ds.probe && C.probe_res) {
     k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
     // bounce 0: and the primary rays k_generate_shade shaded (one more word, 0 without it)
@@ -4598,25 +4690,16 @@ bool Renderer::launch_extend(const LaunchCtx& C, const float4* ro, const float4*
 // The shadow stream of C's lane, rays 0..*cnt-1 (trav_sh_ as launch_extend).
 bool Renderer::launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* occ_out, std::string& err) {
   const PathSet& L = *C.ps;
-  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0) | (trav_sh_ << 2);
+  const int v = trav_variant(ds_.tri_only, C.count, trav_sh_);
   const int full = C.batch_lanes == 1 ? kTravVariants : 0;
   const uint32_t g = std::min(async_grid(C, grid_sh_[v + full], 100), spill_grid(L));
   DevScene ds = ds_;
   ds.probe = probe_slot(C, 3, g);
-#define WPT_SH(T, CN, F)                                                                                        \
-  k_shadow<T, CN, F><<<g, kTBlock, 0, C.stream>>>(ds, cnt, L.so, L.sd, L.sc, L.col, occ_out, L.spill, d_work_, \
-                                                 d_fallback_)
-  switch (v) {
-    case 0: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, false, 0)); break;
-    case 1: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, false, 0)); break;
-    case 2: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, true, 0)); break;
-    case 3: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, true, 0)); break;
-    case 4: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, false, 1)); break;
-    case 5: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, false, 1)); break;
-    case 6: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(false, true, 1)); break;
-    default: LAUNCH_TIMED(C, 3, shadow, n_shadow, WPT_SH(true, true, 1)); break;
-  }
-#undef WPT_SH
+  const auto launch = [&] {
+    kShadowTable[v]<<<g, kTBlock, 0, C.stream>>>(ds, cnt, L.so, L.sd, L.sc, L.col, occ_out, L.spill, d_work_,
+                                                d_fallback_);
+  };
+  if (!launch_timed(C, 3, launch, err)) return false;
   // (cnt is the bounce's sh_count: its resolved slot lies kShResWord - 3 words on)
   if (ds.probe && C.probe_res) {
     k_probe_add_sh<<<1, 1, 0, C.stream>>>(ds.probe, cnt + (kShResWord - 3));
@@ -4630,22 +4713,17 @@ bool Renderer::launch_shadow(const LaunchCtx& C, const uint32_t* cnt, uint8_t* o
 bool Renderer::launch_trace(const LaunchCtx& C, std::string& err) {
   const PathSet& L = *C.ps;
   const int b = C.bounce;
-  const int v = (ds_.tri_only ? 1 : 0) | (C.count ? 2 : 0);
+  const int v = trace_variant(ds_.tri_only, C.count);
   // extension + shadow rays
   const uint32_t g = std::min(async_grid(C, grid_tr_[v], trace_grid_pct_, 2), spill_grid(L));
   DevScene ds = ds_;
   ds.probe = probe_slot(C, 5, g);
-#define WPT_TR(T, CN)                                                                                          \
-  k_trace<T, CN><<<g, kTBlock, 0, C.stream>>>(ds, L.ro[b & 1], L.rd[b & 1], L.ext_count(b), L.hit_t(C.hit_sel), \
-                                             L.hit_id(C.hit_sel), L.sh_count(b - 1), L.so, L.sd, L.sc, L.col,  \
-                                             L.spill, d_work_)
-  switch (v) {
-    case 0: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(false, false)); break;
-    case 1: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(true, false)); break;
-    case 2: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(false, true)); break;
-    default: LAUNCH_TIMED(C, 5, trace, n_trace, WPT_TR(true, true)); break;
-  }
-#undef WPT_TR
+  const auto launch = [&] {
+    kTraceTable[v]<<<g, kTBlock, 0, C.stream>>>(ds, L.ro[b & 1], L.rd[b & 1], L.ext_count(b), L.hit_t(C.hit_sel),
+                                               L.hit_id(C.hit_sel), L.sh_count(b - 1), L.so, L.sd, L.sc, L.col,
+                                               L.spill, d_work_);
+  };
+  if (!launch_timed(C, 5, launch, err)) return false;
   if (ds.probe && C.probe_res) {
     k_probe_add<<<1, 1, 0, C.stream>>>(ds.probe, C.probe_res);
     k_probe_add_sh<<<1, 1, 0, C.stream>>>(ds.probe, L.sh_count(b - 1) + (kShResWord - 3));
@@ -4725,59 +4803,40 @@ uint32_t Renderer::max_grid() const {
 }
 
 bool Renderer::size_grids(std::string& err) {
-  int bpc = 0;
-#define WPT_OCC(arr, idx, K)                                                      \
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, K, (int)kTBlock, 0)); \
-  arr[idx] = (uint32_t)std::max(1, ncu_ * (bpc > 0 ? bpc : 1) * pct / 100);
+  // the persistent grid of `kernel`: pct % of its resident blocks on the chip
+  const auto grid_of = [&](auto kernel, int pct, uint32_t& grid) {
+    uint32_t bpc = 0;
+    if (!occupancy(kernel, kTBlock, 0, bpc, err)) return false;
+    grid = (uint32_t)std::max(1, ncu_ * (int)bpc * pct / 100);
+    return true;
+  };
   // The separate extend / shadow kernels (whole-frame batches, 4 concurrent
   // lanes) get persistent grids of half the resident capacity, so two lanes'
   // traversal kernels run side by side instead of one filling the GPU and the
   // next one's blocks starting only as its blocks drain (C3 +4.5 % with 4
   // lanes); the fused k_trace of small batches keeps full grids.
   // One-lane batches (wpt_set_lanes(1), tiny batches) use every resident
-  // slot: [8 + v] (a half grid left half the GPU idle there).
+  // slot: [kTravVariants + v] (a half grid left half the GPU idle there).
   for (int full = 0; full < 2; full++) {
     const int pct = full ? 100 : grid_pct_;
     const int o = full ? kTravVariants : 0;
-    WPT_OCC(grid_ext_, o + 0, (k_extend<false, false, 0>));
-    WPT_OCC(grid_ext_, o + 1, (k_extend<true, false, 0>));
-    WPT_OCC(grid_ext_, o + 2, (k_extend<false, true, 0>));
-    WPT_OCC(grid_ext_, o + 3, (k_extend<true, true, 0>));
-    WPT_OCC(grid_ext_, o + 4, (k_extend<false, false, 1>));
-    WPT_OCC(grid_ext_, o + 5, (k_extend<true, false, 1>));
-    WPT_OCC(grid_ext_, o + 6, (k_extend<false, true, 1>));
-    WPT_OCC(grid_ext_, o + 7, (k_extend<true, true, 1>));
-    WPT_OCC(grid_sh_, o + 0, (k_shadow<false, false, 0>));
-    WPT_OCC(grid_sh_, o + 1, (k_shadow<true, false, 0>));
-    WPT_OCC(grid_sh_, o + 2, (k_shadow<false, true, 0>));
-    WPT_OCC(grid_sh_, o + 3, (k_shadow<true, true, 0>));
-    WPT_OCC(grid_sh_, o + 4, (k_shadow<false, false, 1>));
-    WPT_OCC(grid_sh_, o + 5, (k_shadow<true, false, 1>));
-    WPT_OCC(grid_sh_, o + 6, (k_shadow<false, true, 1>));
-    WPT_OCC(grid_sh_, o + 7, (k_shadow<true, true, 1>));
+    for (int v = 0; v < kTravVariants; v++)
+      if (!grid_of(kExtendTable[v], pct, grid_ext_[o + v])) return false;
+    for (int v = 0; v < kTravVariants; v++)
+      if (!grid_of(kShadowTable[v], pct, grid_sh_[o + v])) return false;
   }
-  const int pct = trace_grid_pct_;
-  WPT_OCC(grid_tr_, 0, (k_trace<false, false>));
-  WPT_OCC(grid_tr_, 1, (k_trace<true, false>));
-  WPT_OCC(grid_tr_, 2, (k_trace<false, true>));
-  WPT_OCC(grid_tr_, 3, (k_trace<true, true>));
-#undef WPT_OCC
+  for (int v = 0; v < kTraceVariants; v++)
+    if (!grid_of(kTraceTable[v], trace_grid_pct_, grid_tr_[v])) return false;
   {
-    // k_shade: 1024-lane blocks; the smallest occupancy of its variants
-    int m = 1 << 30;
-#define WPT_SHOCC(...)                                                                                    \
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, __VA_ARGS__, (int)kShadeBlock, 0)); \
-  m = std::min(m, bpc);
-    WPT_SHOCC(k_shade<true, false, 0>)
-    WPT_SHOCC(k_shade<true, true, 0>)
-    WPT_SHOCC(k_shade<true, true, 1>)
-    WPT_SHOCC(k_shade<true, true, 2>)
-    WPT_SHOCC(k_shade<false, false, 0>)
-    WPT_SHOCC(k_shade<false, true, 0>)
-    WPT_SHOCC(k_shade<false, true, 1>)
-    WPT_SHOCC(k_shade<false, true, 2>)
-#undef WPT_SHOCC
-    grid_shade_ = (uint32_t)(ncu_ * std::max(m, 1));
+    // k_shade: 1024-lane blocks; the smallest occupancy of its plain variants
+    // (CR = PS = false) without dynamic LDS
+    uint32_t m = 1u << 30;
+    for (int v = 0; v < shade_variant(false, false, 0, true, false); v++) {
+      uint32_t bpc = 0;
+      if (!occupancy(kShadeTable[v], kShadeBlock, 0, bpc, err)) return false;
+      m = std::min(m, bpc);
+    }
+    grid_shade_ = (uint32_t)ncu_ * m;
   }
   // global spill area for stack entries beyond the LDS slots
   const uint32_t gmax = max_grid();
@@ -5201,10 +5260,8 @@ bool Renderer::build_photons(std::string& err) {
       L.h_counts[0] = R;
       HIP_OK(hipMemcpyAsync(L.counts, L.h_counts, 4, hipMemcpyHostToDevice, stream_));
       if (!launch_extend(C, L.ro[0], L.rd[0], L.counts, err)) return false;
-      if (ds_.tri_only)
-        k_photon_hit<true><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, L.ro[0], L.rd[0], L.t, L.id, L.thr[0], L.col, L.pixel);
-      else
-        k_photon_hit<false><<<blocks_for(R), kBlock, 0, stream_>>>(ds_, R, L.ro[0], L.rd[0], L.t, L.id, L.thr[0], L.col, L.pixel);
+      kPhotonHitTable[scene_variant(ds_.tri_only)]<<<blocks_for(R), kBlock, 0, stream_>>>(
+          ds_, R, L.ro[0], L.rd[0], L.t, L.id, L.thr[0], L.col, L.pixel);
       HIP_OK(hipGetLastError());
       HIP_OK(hipMemcpyAsync(hit.data(), L.col, sizeof(float4) * R, hipMemcpyDeviceToHost, stream_));
       HIP_OK(hipMemcpyAsync(lid.data(), L.pixel, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, stream_));
@@ -5300,9 +5357,8 @@ int Renderer::photon_sample(size_t n, const float* pts3, const uint32_t* states,
   HIP_OK(hipMemcpyAsync(ds, states, 4 * n, hipMemcpyHostToDevice, stream_));
   const uint32_t nn = (uint32_t)n, grid = (nn + kShadeBlock - 1) / kShadeBlock;
   const size_t smem = 4 * (size_t)S.oct_lds_words;
-  if (view == 2) k_photon_sample<2><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
-  else if (view == 1) k_photon_sample<1><<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
-  else k_photon_sample<0><<<grid, kShadeBlock, 0, stream_>>>(S, nn, dp, ds, dl, df, dso);
+  // (view is 0, 1 or 2 here; view 0 stages nothing: smem is 0)
+  kPhotonSampleTable[oct_variant(view)]<<<grid, kShadeBlock, smem, stream_>>>(S, nn, dp, ds, dl, df, dso);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(light, dl, 4 * n, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipMemcpyAsync(pdf, df, 4 * n, hipMemcpyDeviceToHost, stream_));
@@ -5425,8 +5481,7 @@ bool Renderer::first_hit_launch(uint32_t sample, uint32_t mask, FhPlanes& planes
   ds.probe = nullptr;
   ds.overflow = (uint32_t*)buf.get();
   HIP_OK(hipMemsetAsync(buf, 0, sizeof(uint32_t), stream_));
-  if (ds_.tri_only) k_first_hit<true><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
-  else k_first_hit<false><<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
+  kFirstHitTable[scene_variant(ds_.tri_only)]<<<g, kTBlock, 0, stream_>>>(ds, P, d_fh_spill_);
   HIP_OK(hipGetLastError());
   uint32_t flag = 0;
   HIP_OK(hipMemcpyAsync(&flag, buf, sizeof flag, hipMemcpyDeviceToHost, stream_));
