@@ -768,6 +768,62 @@ int wpt_radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32
                       uint32_t type, uint32_t flags, float* rgb3, uint8_t* status);
 /* Host only (no session, no GPU): the status rule above on n rays. */
 int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status);
+/* First-hit feature planes along a caller's rays: wpt_first_hit's planes for
+ * rays that are not the session camera's (the guide planes of a fisheye,
+ * panorama, orthographic or stereo frame traced through wpt_radiance_rays).
+ * Ray i = {ox,oy,oz,dx,dy,dz} as wpt_radiance_rays takes it, the direction used
+ * as given; entry i of every plane is what wpt_first_hit gives a pixel whose
+ * primary ray is ray i (n entries each; any pointer may be NULL = neither
+ * computed nor stored):
+ *  t       f32    Scene::trace distance, +inf on a miss
+ *  id      i32    shape id in the scene's reordered shape list, -1 on a miss
+ *  visits  u32    the reference's num_bvh_hits of this ray
+ *  normal3 3 f32  Hit.normal (faces the ray); +0 on a miss
+ *  albedo3 3 f32  Diffuse colour, or the Emissive intensity; +0 on a miss
+ *  kind    u8     0 miss, 1 diffuse, 2 emissive
+ *  status  u8     wpt_rays_valid's rule: 1 traced, 0 not
+ * The hit is found by the exact BVH2 on every scene. A ray of status 0 is never
+ * started: t +inf, id -1, visits 0, normal and albedo +0, kind 0. With
+ * rays6 = wpt_primary_rays(W, H, cam, seed, s) the planes are wpt_first_hit(s)
+ * of a W x H session under that camera and seed, visits included. Ray i's
+ * entries depend on that ray and the scene only. The call needs a session and
+ * a scene, no viewport, and works in a buffer of its own: the session
+ * (accumulation, rounds, sample stock, history, sample map and map mode,
+ * wpt_stats, wpt_kernel_times) and the guide planes wpt_denoise, wpt_reproject,
+ * wpt_upsample and wpt_sample_map keep on the device are not touched. flags:
+ * WPT_RAYS_DEVICE: every pointer is a device pointer on the session's device
+ * (the call still returns synchronised). With every output NULL, or n == 0,
+ * nothing is launched and the call succeeds.
+ * WPT_ERR_INVALID_ARG, with nothing launched and nothing written: n > 0 with an
+ * output wanted and a null rays6, an unknown flag, n >= 2^32. WPT_ERR_DEVICE if
+ * the traversal stack overflowed, as for wpt_first_hit. */
+int wpt_first_hit_rays(size_t n, const float* rays6, uint32_t flags, float* t, int32_t* id, uint32_t* visits,
+                       float* normal3, float* albedo3, uint8_t* kind, uint8_t* status);
+/* A filtered frame along a W x H grid of a caller's rays: ray y * W + x is pixel
+ * (x, y). A composition of three public calls, kept on the device:
+ *  raw3, status       what wpt_radiance_rays(W * H, rays6, keys, sample, spp, type,
+ *                     ...) gives; wpt_stats and wpt_kernel_times grow, and the
+ *                     session is left, exactly as by that call
+ *  rgb3, valid, rgba  wpt_denoise_host(W, H, acc3 = raw3, cnt, t, normal3, albedo3,
+ *                     kind, iterations, sigma_c, sigma_z, dn_flags) with
+ *                     cnt[i] = spp * status[i] and the guide planes
+ *                     wpt_first_hit_rays gives for the same rays, bit for bit
+ *                     while |acc / cnt| <= 2^100 (wpt_denoise's bound)
+ * The sums, the counts, the guide planes and the filter's scratch stay on the
+ * device from the first launch to the last; only the outputs asked for are
+ * copied. A grid of more rays than the query traces at a time is still filtered
+ * as one frame. WPT_OPT_DENOISE_LDS chooses the kernels as for wpt_denoise.
+ * flags: WPT_RAYS_DEVICE: every pointer is a device pointer. Any output may be
+ * NULL; with all five NULL nothing is launched. Accumulating over several calls
+ * is the caller's, as with wpt_radiance_rays.
+ * WPT_ERR_INVALID_ARG, with nothing launched and nothing written: W * H == 0 or
+ * >= 2^32, a null rays6, spp 0, type > 2, sample + spp - 1 > 2^32 - 1,
+ * iterations 0 or above 5, a sigma not finite or <= 0, an unknown bit in flags
+ * or dn_flags. The definition to the operation: DESIGN.md §2. */
+int wpt_denoise_rays(uint32_t W, uint32_t H, const float* rays6, const uint32_t* keys, uint32_t sample,
+                     uint32_t spp, uint32_t type, uint32_t iterations, float sigma_c, float sigma_z,
+                     uint32_t dn_flags, uint32_t flags, float* rgb3, uint8_t* valid, uint8_t* rgba,
+                     float* raw3, uint8_t* status);
 /* Test hook: the producers' presolve of extension rays (WPT_OPT_PRESOLVE) on
  * the device for n rays {ox,oy,oz,dx,dy,dz}: resolved[i] = 1 if ray i needs no
  * traversal; (t, id) is then its closest hit (a plane, or +inf and -1). */

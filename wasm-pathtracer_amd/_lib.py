@@ -83,6 +83,9 @@ _SIGS = {
     "wpt_compute_map": (ctypes.c_int, [c_p]),
     "wpt_radiance_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
     "wpt_rays_valid": (ctypes.c_int, [c_sz, c_p, c_p]),
+    "wpt_first_hit_rays": (ctypes.c_int, [c_sz, c_p, c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "wpt_denoise_rays": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_u32, c_u32,
+                                        c_p, c_p, c_p, c_p, c_p]),
     "wpt_presolve_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_presolve": (ctypes.c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "wpt_debug_scene_guards": (ctypes.c_int, [c_p, c_p, c_p, c_p]),

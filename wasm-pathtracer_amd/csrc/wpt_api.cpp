@@ -1144,6 +1144,39 @@ int wpt_radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32
   return WPT_OK;
 }
 
+int wpt_first_hit_rays(size_t n, const float* rays6, uint32_t flags, float* t, int32_t* id, uint32_t* visits,
+                       float* normal3, float* albedo3, uint8_t* kind, uint8_t* status) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  const bool wanted = t || id || visits || normal3 || albedo3 || kind || status;
+  if (flags & ~(uint32_t)WPT_RAYS_DEVICE) return fail(WPT_ERR_INVALID_ARG, "first_hit_rays: unknown flag");
+  if ((uint64_t)n >= (1ull << 32)) return fail(WPT_ERR_INVALID_ARG, "first_hit_rays: 2^32 rays or more");
+  if (n && wanted && !rays6) return fail(WPT_ERR_INVALID_ARG, "first_hit_rays: null rays6");
+  std::string err;
+  if (!g_session->renderer.first_hit_rays(n, rays6, (flags & WPT_RAYS_DEVICE) != 0, t, id, visits, normal3, albedo3, kind,
+                                          status, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+int wpt_denoise_rays(uint32_t W, uint32_t H, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                     uint32_t type, uint32_t iterations, float sigma_c, float sigma_z, uint32_t dn_flags, uint32_t flags,
+                     float* rgb3, uint8_t* valid, uint8_t* rgba, float* raw3, uint8_t* status) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  const uint64_t n = (uint64_t)W * H;
+  if (n == 0 || n >= (1ull << 32)) return fail(WPT_ERR_INVALID_ARG, "denoise_rays: W * H is 0, or 2^32 or more");
+  // radiance_rays' rules (its rgb3 may be null here: raw3 is one output of five)
+  const float nonnull = 0.0f;
+  if (const char* e = radiance_rays_args((size_t)n, rays6, sample, spp, type, flags, &nonnull))
+    return fail(WPT_ERR_INVALID_ARG, e);
+  if (const char* e = denoise_args(iterations, sigma_c, sigma_z, dn_flags)) return fail(WPT_ERR_INVALID_ARG, e);
+  std::string err;
+  if (!g_session->renderer.denoise_rays(W, H, rays6, keys, sample, spp, type,
+                                        DnParams{iterations, sigma_c, sigma_z, dn_flags},
+                                        (flags & WPT_RAYS_DEVICE) != 0, rgb3, valid, rgba, raw3, status, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
 int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status) {
   if (n && (!rays6 || !status)) return fail(WPT_ERR_INVALID_ARG, "null argument");
   for (size_t i = 0; i < n; i++) status[i] = ray_valid(rays6 + 6 * i) ? 1 : 0;

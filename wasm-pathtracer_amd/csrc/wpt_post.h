@@ -96,8 +96,12 @@ class FramePost {
   // the guides). Everything is queued on F.stream, neither timed nor counted,
   // and waited for; the frame is only read.
   //
-  // the a-trous filter on the frame under guides t, normal, albedo, kind
-  bool denoise(const FrameRef& F, const Guides& g, const DnParams& P, const PostOut& O, std::string& err);
+  // the a-trous filter on the frame under guides t, normal, albedo, kind. The
+  // frame need not be the session's (wpt_denoise_rays hands in a query's sums
+  // and counts: F.cam is not read): the scratch grows to the frame at hand and
+  // is still freed with the viewport. dev_out: O's are device pointers.
+  bool denoise(const FrameRef& F, const Guides& g, const DnParams& P, const PostOut& O, std::string& err,
+               bool dev_out = false);
   // the same over the merged frame and the guides the last reproject left
   bool denoise_merged(const FrameRef& F, const DnParams& P, const PostOut& O, std::string& err);
   // the kept history into the frame's camera, merged with the frame; the merged

@@ -124,11 +124,13 @@ static_assert(kScanChunk == 1024 && MapLayout(5000).nb == 5 && MapLayout(5000).b
 bool wanted(const PostOut& O) { return O.rgb3 || O.valid || O.rgba; }
 
 // The device outputs that were asked for (the null ones are not looked at) of
-// n pixels to the host, then waits for s.
-bool copy_out(hipStream_t s, const PostOut& O, const PostOut& dev, size_t n, std::string& err) {
-  if (O.rgb3) HIP_OK(hipMemcpyAsync(O.rgb3, dev.rgb3, 12 * n, hipMemcpyDeviceToHost, s));
-  if (O.valid) HIP_OK(hipMemcpyAsync(O.valid, dev.valid, n, hipMemcpyDeviceToHost, s));
-  if (O.rgba) HIP_OK(hipMemcpyAsync(O.rgba, dev.rgba, 4 * n, hipMemcpyDeviceToHost, s));
+// n pixels to the host (dev_out: to the caller's device pointers), then waits
+// for s.
+bool copy_out(hipStream_t s, const PostOut& O, const PostOut& dev, size_t n, std::string& err, bool dev_out = false) {
+  const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (O.rgb3) HIP_OK(hipMemcpyAsync(O.rgb3, dev.rgb3, 12 * n, kind, s));
+  if (O.valid) HIP_OK(hipMemcpyAsync(O.valid, dev.valid, n, kind, s));
+  if (O.rgba) HIP_OK(hipMemcpyAsync(O.rgba, dev.rgba, 4 * n, kind, s));
   HIP_OK(hipStreamSynchronize(s));
   return true;
 }
@@ -229,7 +231,7 @@ bool dn_passes(const FrameRef& F, const Guides& g, const DnParams& P, uint32_t l
 // The filter over device planes: dn_passes, then unpack; the outputs wanted
 // are copied to the host and waited for.
 bool dn_run(const FrameRef& F, const Guides& g, const DnParams& P, uint32_t lds_mask, char* scratch, const PostOut& O,
-            std::string& err) {
+            std::string& err, bool dev_out = false) {
   DnRecords R;
   if (!dn_passes(F, g, P, lds_mask, scratch, R, err)) return false;
   const size_t np = (size_t)F.W * F.H;
@@ -238,7 +240,7 @@ bool dn_run(const FrameRef& F, const Guides& g, const DnParams& P, uint32_t lds_
                        O.rgba ? (uint8_t*)(scratch + Z.rgba) : nullptr};
   k_dn_unpack<<<blocks_for(np), kBlock, 0, F.stream>>>(R.A, R.B, R.ap, (uint32_t)np, dev.rgb3, dev.valid, dev.rgba);
   HIP_OK(hipGetLastError());
-  return copy_out(F.stream, O, dev, np, err);
+  return copy_out(F.stream, O, dev, np, err, dev_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -339,9 +341,10 @@ const uint32_t* FramePost::map_counts(uint64_t epoch, size_t np) const {
   return (const uint32_t*)(d_map_ + MapLayout(np).count);
 }
 
-bool FramePost::denoise(const FrameRef& F, const Guides& g, const DnParams& P, const PostOut& O, std::string& err) {
+bool FramePost::denoise(const FrameRef& F, const Guides& g, const DnParams& P, const PostOut& O, std::string& err,
+                        bool dev_out) {
   HIP_OK(d_dn_.grow(DnLayout((size_t)F.W * F.H).bytes));
-  return dn_run(F, g, P, dn_lds_, d_dn_, O, err);
+  return dn_run(F, g, P, dn_lds_, d_dn_, O, err, dev_out);
 }
 
 bool FramePost::denoise_planes(hipStream_t s, const HostFrame& h, const Guides& hg, const DnParams& P,

@@ -288,7 +288,7 @@ constexpr int shade_variant(bool tri_only, bool pnee, int oct, bool cr, bool ps)
 constexpr int finish_variant(bool tri_only, bool pnee, bool cr) {
   return (tri_only ? 1 : 0) | (pnee ? 2 : 0) | (cr ? 4 : 0);
 }
-// k_generate_shade, k_first_hit, k_photon_hit
+// k_generate_shade, k_first_hit, k_first_hit_rays, k_photon_hit
 constexpr int scene_variant(bool tri_only) { return tri_only ? 1 : 0; }
 // k_photon_sample: the octree view itself
 constexpr int oct_variant(int view) { return view; }
@@ -417,6 +417,26 @@ class Renderer {
   // touched. The caller checks the arguments.
   bool radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
                      bool device, float* rgb3, uint8_t* status, std::string& err);
+  // first_hit's planes along a caller's rays (wpt_first_hit_rays.h,
+  // wpt_first_hit_rays): entry i is what first_hit gives a pixel whose primary
+  // ray is rays6[i]; status as radiance_rays gives it; a null plane is neither
+  // computed nor stored. device: every pointer is a device pointer. Needs a
+  // scene, no viewport; works in d_fhr_, so first_hit's buffers, which keep the
+  // guides of the filter, the reprojection and the sample map, the frame, the
+  // rounds, the counters and the timings are neither read nor written. Host
+  // rays go through in chunks of kQueryChunk. The caller checks the arguments.
+  bool first_hit_rays(size_t n, const float* rays6, bool device, float* t, int32_t* id, uint32_t* visits,
+                      float* normal3, float* albedo3, uint8_t* kind, uint8_t* status, std::string& err);
+  // The a-trous filter on a W x H frame of a caller's rays (wpt_denoise_rays):
+  // radiance_rays' sums of the rays (raw3, status), first_hit_rays' guide planes
+  // of the same rays and post_.denoise over both with cnt = spp * status; the
+  // sums, the counts, the planes and the filter's scratch stay on the device
+  // (d_rayframe_, one frame whatever the query's chunks). The session is left
+  // as radiance_rays leaves it. A null output is not written; with all five
+  // null nothing is launched. The caller checks the arguments.
+  bool denoise_rays(uint32_t W, uint32_t H, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                    uint32_t type, const DnParams& P, bool device, float* rgb3, uint8_t* valid, uint8_t* rgba,
+                    float* raw3, uint8_t* status, std::string& err);
   // WPT_OPT_MAP_MODE: a map was traced in this accumulation (wpt_compute is an
   // error until the next reset)
   bool map_mode() const { return map_mode_; }
@@ -803,6 +823,32 @@ class Renderer {
   // lanes
   DevBuf<char> d_query_;
   PinBuf<char> h_query_;
+  // The chunks of a query: radiance_rays' body. sums / cnts non-null: the n
+  // rays' float4 sums and counts go there (device, entry i = ray i: one frame
+  // over all chunks; rays6, keys, rgb3 and status are then device pointers)
+  // and rgb3 may be null: no packed copy is made.
+  bool query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
+                    bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts, std::string& err);
+  // first_hit_rays' own buffers, kept between calls and freed with first_hit's:
+  // the overflow flag, then for host pointers a chunk's rays, planes and status;
+  // the traversal-stack spill area of its grid
+  DevBuf<char> d_fhr_;
+  DevBuf<uint2> d_fhr_spill_;
+  struct FhrPlanes {  // device pointers; a plane outside the launch's mask is not looked at
+    float* t = nullptr;
+    int32_t* id = nullptr;
+    uint32_t* visits = nullptr;
+    float* normal = nullptr;
+    float* albedo = nullptr;
+    uint8_t* kind = nullptr;
+  };
+  // k_first_hit_rays of the planes in `mask` over n device rays into P; returns
+  // once the kernel has ended without a stack overflow
+  bool first_hit_rays_launch(uint32_t n, const float* d_rays, uint32_t mask, const FhrPlanes& P, std::string& err);
+  // denoise_rays' frame: the sums, the counts, the guide planes and the status
+  // of every ray, for host pointers also the rays, the keys and the packed
+  // sums; freed with the lanes
+  DevBuf<char> d_rayframe_;
   bool compute_end(std::string& err);  // what every tracing call ends with: counts, overflow flag, work counters
   hipStream_t stream_ = nullptr;
   PathSet lanes_[kMaxLanes];

@@ -2575,6 +2575,7 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 // the query generators (last, so that the functions above keep their order)
 #define WPT_RAYS_KERNELS
 #include "wpt_rays.h"
+#include "wpt_first_hit_rays.h"
 
 // ===========================================================================
 // Kernel variant tables
@@ -2649,6 +2650,11 @@ struct FirstHitAt {
   static constexpr int index = scene_variant(V != 0);
 };
 template <size_t V>
+struct FirstHitRaysAt {
+  static constexpr auto fn = &k_first_hit_rays<V != 0>;
+  static constexpr int index = scene_variant(V != 0);
+};
+template <size_t V>
 struct PhotonHitAt {
   static constexpr auto fn = &k_photon_hit<V != 0>;
   static constexpr int index = scene_variant(V != 0);
@@ -2666,6 +2672,7 @@ constexpr auto kShadeTable = variant_table<ShadeAt>(Variants<kShadeVariants>{});
 constexpr auto kFinishTable = variant_table<FinishAt>(Variants<kFinishVariants>{});
 constexpr auto kGenShadeTable = variant_table<GenShadeAt>(Variants<kSceneVariants>{});
 constexpr auto kFirstHitTable = variant_table<FirstHitAt>(Variants<kSceneVariants>{});
+constexpr auto kFirstHitRaysTable = variant_table<FirstHitRaysAt>(Variants<kSceneVariants>{});
 constexpr auto kPhotonHitTable = variant_table<PhotonHitAt>(Variants<kSceneVariants>{});
 constexpr auto kPhotonSampleTable = variant_table<PhotonSampleAt>(Variants<kOctVariants>{});
 
@@ -2676,6 +2683,7 @@ static_assert(variant_table_ok<ShadeAt>(Variants<kShadeVariants>{}), "k_shade's 
 static_assert(variant_table_ok<FinishAt>(Variants<kFinishVariants>{}), "k_finish's table");
 static_assert(variant_table_ok<GenShadeAt>(Variants<kSceneVariants>{}), "k_generate_shade's table");
 static_assert(variant_table_ok<FirstHitAt>(Variants<kSceneVariants>{}), "k_first_hit's table");
+static_assert(variant_table_ok<FirstHitRaysAt>(Variants<kSceneVariants>{}), "k_first_hit_rays' table");
 static_assert(variant_table_ok<PhotonHitAt>(Variants<kSceneVariants>{}), "k_photon_hit's table");
 static_assert(variant_table_ok<PhotonSampleAt>(Variants<kOctVariants>{}), "k_photon_sample's table");
 // spot checks in plain words: one entry per family, named by its flags
@@ -2687,6 +2695,7 @@ static_assert(kExtendTable[trav_variant(true, false, 1)] == &k_extend<true, fals
                   kFinishTable[finish_variant(false, true, true)] == &k_finish<false, true, true> &&
                   kGenShadeTable[scene_variant(true)] == &k_generate_shade<true> &&
                   kFirstHitTable[scene_variant(false)] == &k_first_hit<false> &&
+                  kFirstHitRaysTable[scene_variant(true)] == &k_first_hit_rays<true> &&
                   kPhotonHitTable[scene_variant(true)] == &k_photon_hit<true> &&
                   kPhotonSampleTable[oct_variant(1)] == &k_photon_sample<1>,
               "the tables' numbering");
@@ -2823,6 +2832,8 @@ Renderer::~Renderer() {
   d_fallback_.reset();
   d_fh_.reset();
   d_fh_spill_.reset();
+  d_fhr_.reset();
+  d_fhr_spill_.reset();
   h_word_.reset();
   for (PathSet& L : lanes_) {
     L.counts.reset();
@@ -2909,6 +2920,7 @@ void Renderer::free_paths() {
   for (PathSet& L : lanes_) free_lane_paths(L);
   d_query_.reset();
   h_query_.reset();
+  d_rayframe_.reset();
 }
 
 bool Renderer::upload_scene(const HostScene& sc, std::string& err) {
@@ -5678,6 +5690,14 @@ struct QueryLayout {
 
 bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
                              uint32_t type, bool device, float* rgb3, uint8_t* status, std::string& err) {
+  return query_chunks(n, rays6, keys, sample, spp, type, device, rgb3, status, nullptr, nullptr, err);
+}
+
+// sums: the chunk at c0 adds to entries c0 .. of the caller's frame (denoise_rays)
+// and takes nothing of d_query_.
+bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                            uint32_t type, bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts,
+                            std::string& err) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   // refills and fill batches in flight use the lanes this call may resize
@@ -5688,12 +5708,12 @@ bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys,
     const size_t cn = std::min(kQueryChunk, n - c0);
     const uint32_t cnn = (uint32_t)cn;
     const QueryLayout Q(cn, !device, keys != nullptr);
-    HIP_OK(d_query_.grow(Q.bytes));
+    if (!sums) HIP_OK(d_query_.grow(Q.bytes));
     char* m = d_query_;
     RayQuery R;
-    R.acc = (float4*)(m + Q.acc);
-    R.cnt = (uint32_t*)(m + Q.cnt);
-    float* d_rgb = rgb3 + 3 * c0;
+    R.acc = sums ? sums + c0 : (float4*)(m + Q.acc);
+    R.cnt = sums ? cnts + c0 : (uint32_t*)(m + Q.cnt);
+    float* d_rgb = rgb3 ? rgb3 + 3 * c0 : nullptr;
     uint8_t* d_status = status ? status + c0 : nullptr;
     char* hp = nullptr;
     if (device) {
@@ -5718,7 +5738,12 @@ bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys,
     R.spp = spp;
     R.sample = sample;
     R.type = type;
-    HIP_OK(hipMemsetAsync(m, 0, Q.sums_end, stream_));  // the sums and counts
+    if (sums) {
+      HIP_OK(hipMemsetAsync(R.acc, 0, sizeof(float4) * cn, stream_));
+      HIP_OK(hipMemsetAsync(R.cnt, 0, sizeof(uint32_t) * cn, stream_));
+    } else {
+      HIP_OK(hipMemsetAsync(m, 0, Q.sums_end, stream_));  // the sums and counts
+    }
     if (status) {
       k_rays_status<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.rays, d_status);
       HIP_OK(hipGetLastError());
@@ -5738,8 +5763,10 @@ bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys,
     for (uint64_t k0 = 0; k0 < total; k0 += cap)
       if (!run_batch(k0, std::min<uint64_t>(cap, total - k0), -1, err, nullptr, 0, &M)) return false;
     // (the main stream has waited for every lane's accumulation: batch_tail)
-    k_rays_unpack<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.acc, d_rgb);
-    HIP_OK(hipGetLastError());
+    if (d_rgb) {
+      k_rays_unpack<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.acc, d_rgb);
+      HIP_OK(hipGetLastError());
+    }
     if (!device) {
       const size_t back = (status ? Q.status + cn : Q.rgb + 3 * sizeof(float) * cn) - Q.rgb;
       HIP_OK(hipMemcpyAsync(hp + Q.rgb, m + Q.rgb, back, hipMemcpyDeviceToHost, stream_));
@@ -5751,6 +5778,169 @@ bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys,
     }
   }
   return compute_end(err);
+}
+
+// ---------------------------------------------------------------------------
+// First-hit planes and the filter along a caller's rays (wpt_first_hit_rays.h)
+// ---------------------------------------------------------------------------
+
+namespace {
+// first_hit_rays' buffer: the overflow flag; for host pointers then a chunk's
+// rays, the planes of `mask` (kFh* order from kFhT on) and the status bytes
+struct FhrLayout {
+  size_t rays = 0, off[7] = {}, status = 0, bytes = 0;
+  constexpr FhrLayout(size_t n, uint32_t mask, bool want_status) {
+    Slices z;
+    z.take(sizeof(uint32_t));
+    rays = z.take(6 * sizeof(float) * n);
+    for (int k = 1; k < 7; k++) off[k] = (mask >> k & 1u) ? z.take(kFhElem[k] * n) : z.at;
+    status = want_status ? z.take(n) : z.at;
+    bytes = z.at;
+  }
+};
+static_assert(FhrLayout(1000, 0x7Eu, true).rays == 256 && FhrLayout(1000, 0x7Eu, true).off[1] == 24320 &&
+                  FhrLayout(1000, 0x7Eu, true).status == 61696 && FhrLayout(1000, 0x7Eu, true).bytes == 62720,
+              "first_hit_rays' layout");
+// denoise_rays' frame of n rays: the query's sums and counts, the guide planes,
+// the status; for host pointers the rays, the keys and the packed sums
+struct RayFrameLayout {
+  size_t acc = 0, cnt = 0, t = 0, normal = 0, albedo = 0, kind = 0, status = 0, rays = 0, keys = 0, raw = 0, bytes = 0;
+  constexpr RayFrameLayout(size_t n, bool host, bool keyed, bool want_raw) {
+    Slices z;
+    acc = z.take(sizeof(float4) * n); cnt = z.take(sizeof(uint32_t) * n);
+    t = z.take(4 * n); normal = z.take(12 * n); albedo = z.take(12 * n); kind = z.take(n); status = z.take(n);
+    if (host) {
+      rays = z.take(6 * sizeof(float) * n);
+      keys = z.take(keyed ? sizeof(uint32_t) * n : 0);
+      raw = z.take(want_raw ? 3 * sizeof(float) * n : 0);
+    }
+    bytes = z.at;
+  }
+};
+static_assert(RayFrameLayout(1000, false, false, false).bytes == 50432 &&
+                  RayFrameLayout(1000, true, true, true).raw == 78592 &&
+                  RayFrameLayout(1000, true, true, true).bytes == 90624,
+              "denoise_rays' layout");
+}  // namespace
+
+// One block per kTBlock rays, clamped to a spill area of kFhSpillBytes as
+// first_hit_launch clamps it (the blocks then take further rays a grid stride
+// on); the overflow flag is d_fhr_'s first word.
+bool Renderer::first_hit_rays_launch(uint32_t n, const float* d_rays, uint32_t mask, const FhrPlanes& O,
+                                     std::string& err) {
+  HIP_OK(d_fhr_.grow(sizeof(uint32_t)));
+  FirstHitRaysParams P;
+  P.rays = d_rays;
+  P.n = n;
+  P.ngroups = (uint32_t)(((uint64_t)n + 63u) / 64u);
+  P.mask = mask;
+  P.t = O.t; P.id = O.id; P.visits = O.visits; P.normal = O.normal; P.albedo = O.albedo; P.kind = O.kind;
+  constexpr size_t kFhSpillBytes = 256ull << 20;
+  const size_t per_block = spill_slots() * kTBlock * sizeof(uint2);
+  const uint32_t want = (P.ngroups + kTBlock / 64 - 1) / (kTBlock / 64);
+  const uint32_t g = (uint32_t)std::max<size_t>(1, std::min<size_t>(want, kFhSpillBytes / per_block));
+  HIP_OK(d_fhr_spill_.grow((size_t)g * per_block / sizeof(uint2)));
+  DevScene ds = ds_;
+  ds.probe = nullptr;
+  ds.overflow = (uint32_t*)d_fhr_.get();
+  HIP_OK(hipMemsetAsync(d_fhr_, 0, sizeof(uint32_t), stream_));
+  kFirstHitRaysTable[scene_variant(ds_.tri_only)]<<<g, kTBlock, 0, stream_>>>(ds, P, d_fhr_spill_);
+  HIP_OK(hipGetLastError());
+  uint32_t flag = 0;
+  HIP_OK(hipMemcpyAsync(&flag, d_fhr_, sizeof flag, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (flag) { err = "traversal stack overflow (results invalid)"; return false; }
+  return true;
+}
+
+bool Renderer::first_hit_rays(size_t n, const float* rays6, bool device, float* t, int32_t* id, uint32_t* visits,
+                              float* normal3, float* albedo3, uint8_t* kind, uint8_t* status, std::string& err) {
+  const uint32_t mask = (t ? kFhT : 0u) | (id ? kFhId : 0u) | (visits ? kFhVisits : 0u) | (normal3 ? kFhNormal : 0u) |
+                        (albedo3 ? kFhAlbedo : 0u) | (kind ? kFhKind : 0u);
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (n == 0 || (mask == 0 && !status)) return true;
+  if (device) {
+    // the caller's planes are the kernel's: no buffer but the flag, no chunks
+    const uint32_t nn = (uint32_t)n;
+    if (status) {
+      k_rays_status<<<blocks_for(nn), kBlock, 0, stream_>>>(nn, rays6, status);
+      HIP_OK(hipGetLastError());
+    }
+    if (mask) return first_hit_rays_launch(nn, rays6, mask, FhrPlanes{t, id, visits, normal3, albedo3, kind}, err);
+    HIP_OK(hipStreamSynchronize(stream_));
+    return true;
+  }
+  void* host[7] = {nullptr, t, id, visits, normal3, albedo3, kind};
+  for (size_t c0 = 0; c0 < n; c0 += kQueryChunk) {
+    const size_t cn = std::min(kQueryChunk, n - c0);
+    const uint32_t cnn = (uint32_t)cn;
+    const FhrLayout Z(cn, mask, status != nullptr);
+    HIP_OK(d_fhr_.grow(Z.bytes));
+    char* m = d_fhr_;
+    const float* d_rays = (const float*)(m + Z.rays);
+    HIP_OK(hipMemcpyAsync(m + Z.rays, rays6 + 6 * c0, 6 * sizeof(float) * cn, hipMemcpyHostToDevice, stream_));
+    if (status) {
+      k_rays_status<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, d_rays, (uint8_t*)(m + Z.status));
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(status + c0, m + Z.status, cn, hipMemcpyDeviceToHost, stream_));
+    }
+    if (mask) {
+      const FhrPlanes P{(float*)(m + Z.off[1]),  (int32_t*)(m + Z.off[2]), (uint32_t*)(m + Z.off[3]),
+                        (float*)(m + Z.off[4]),  (float*)(m + Z.off[5]),   (uint8_t*)(m + Z.off[6])};
+      if (!first_hit_rays_launch(cnn, d_rays, mask, P, err)) return false;
+      for (int k = 1; k < 7; k++)
+        if (host[k])
+          HIP_OK(hipMemcpyAsync((char*)host[k] + kFhElem[k] * c0, m + Z.off[k], kFhElem[k] * cn, hipMemcpyDeviceToHost,
+                                stream_));
+    }
+    HIP_OK(hipStreamSynchronize(stream_));
+  }
+  return true;
+}
+
+bool Renderer::denoise_rays(uint32_t W, uint32_t H, const float* rays6, const uint32_t* keys, uint32_t sample,
+                            uint32_t spp, uint32_t type, const DnParams& P, bool device, float* rgb3, uint8_t* valid,
+                            uint8_t* rgba, float* raw3, uint8_t* status, std::string& err) {
+  if (!scene_ok_) { err = "no scene"; return false; }
+  if (!rgb3 && !valid && !rgba && !raw3 && !status) return true;
+  const size_t n = (size_t)W * H;
+  const uint32_t nn = (uint32_t)n;
+  const RayFrameLayout Z(n, !device, keys != nullptr, raw3 != nullptr);
+  HIP_OK(d_rayframe_.grow(Z.bytes));
+  char* m = d_rayframe_;
+  float4* acc = (float4*)(m + Z.acc);
+  uint32_t* cnt = (uint32_t*)(m + Z.cnt);
+  uint8_t* d_status = (uint8_t*)(m + Z.status);
+  const float* d_rays = rays6;
+  const uint32_t* d_keys = keys;
+  float* d_raw = raw3;
+  if (!device) {
+    HIP_OK(hipMemcpyAsync(m + Z.rays, rays6, 6 * sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    if (keys) HIP_OK(hipMemcpyAsync(m + Z.keys, keys, sizeof(uint32_t) * n, hipMemcpyHostToDevice, stream_));
+    d_rays = (const float*)(m + Z.rays);
+    d_keys = keys ? (const uint32_t*)(m + Z.keys) : nullptr;
+    d_raw = raw3 ? (float*)(m + Z.raw) : nullptr;
+  }
+  // the traced part: the query's batches, chunk after chunk, into the frame's sums
+  if (!query_chunks(n, d_rays, d_keys, sample, spp, type, true, d_raw, d_status, acc, cnt, err)) return false;
+  const hipMemcpyKind back = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (raw3 && !device) HIP_OK(hipMemcpyAsync(raw3, d_raw, 3 * sizeof(float) * n, back, stream_));
+  if (status) HIP_OK(hipMemcpyAsync(status, d_status, n, back, stream_));
+  if (!rgb3 && !valid && !rgba) {
+    HIP_OK(hipStreamSynchronize(stream_));
+    return true;
+  }
+  // the filter's inputs: cnt = spp * status, the guide planes of the same rays
+  k_rayframe_cnt<<<blocks_for(nn), kBlock, 0, stream_>>>(nn, d_status, spp, cnt);
+  HIP_OK(hipGetLastError());
+  FhrPlanes G;
+  G.t = (float*)(m + Z.t); G.normal = (float*)(m + Z.normal); G.albedo = (float*)(m + Z.albedo);
+  G.kind = (uint8_t*)(m + Z.kind);
+  if (!first_hit_rays_launch(nn, d_rays, kFhGuides, G, err)) return false;
+  Guides g;
+  g.t = G.t; g.normal = G.normal; g.albedo = G.albedo; g.kind = G.kind;
+  const FrameRef F{W, H, acc, cnt, nullptr, ds_.bg, epoch_, stream_};
+  return post_.denoise(F, g, P, PostOut{rgb3, valid, rgba}, err, device);
 }
 
 bool Renderer::presolve_rays(size_t n, const float* rays, uint8_t* resolved, float* t_out, int32_t* id_out,

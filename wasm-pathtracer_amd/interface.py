@@ -511,6 +511,48 @@ def rays_valid(rays):
     return status
 
 
+FIRST_HIT_RAYS_PLANES = {  # name -> (argument position in wpt_first_hit_rays' outputs, dtype, components)
+    "t": (0, np.float32, 1), "id": (1, np.int32, 1), "visits": (2, np.uint32, 1), "normal": (3, np.float32, 3),
+    "albedo": (4, np.float32, 3), "kind": (5, np.uint8, 1), "status": (6, np.uint8, 1),
+}
+
+
+def _device_rays(rays):
+    import torch
+
+    if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 6:
+        raise ValueError("rays: a contiguous float32 tensor of 6 components per ray")
+    return torch, rays.numel() // 6
+
+
+def first_hit_rays(rays, planes=("t", "id", "visits", "normal", "albedo", "kind", "status"), device=False):
+    """First-hit feature planes along a caller's rays (wpt_first_hit_rays): a
+    dict plane name -> (n,) or (n, 3) array of the planes asked for, entry i
+    what first_hit() gives a pixel whose primary ray is rays[i]; `status` is
+    rays_valid()'s byte, and a ray of status 0 gets the miss entries with visits
+    0. device=True: rays is a contiguous float32 torch tensor on the session's
+    device, and so are the planes (id as torch.int32, visits as the bits of a
+    torch.int32). The session is not touched."""
+    out, ptr = {}, [None] * 7
+    if device:
+        torch, n = _device_rays(rays)
+        tdt = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32, np.uint8: torch.uint8}
+        for name in planes:
+            pos, dt, c = FIRST_HIT_RAYS_PLANES[name]
+            out[name] = torch.empty((n, 3) if c == 3 else (n,), dtype=tdt[dt], device=rays.device)
+            ptr[pos] = out[name].data_ptr()
+        _check(lib().wpt_first_hit_rays(n, rays.data_ptr(), RAYS_DEVICE, *ptr))
+        return out
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    for name in planes:
+        pos, dt, c = FIRST_HIT_RAYS_PLANES[name]
+        out[name] = np.empty((n, 3) if c == 3 else (n,), dtype=dt)
+        ptr[pos] = out[name].ctypes.data
+    _check(lib().wpt_first_hit_rays(n, r.ctypes.data, 0, *ptr))
+    return out
+
+
 DENOISE_ALBEDO = 1  # WPT_DENOISE_ALBEDO: filter radiance / albedo on diffuse hits, multiply the albedo back
 # the documented defaults of denoise(): see profiles/denoise/README.md
 DENOISE_DEFAULTS = {"iterations": 3, "sigma_c": 1.0, "sigma_z": 0.1, "flags": DENOISE_ALBEDO}
@@ -567,6 +609,54 @@ def denoise_host(acc, cnt, t, normal, albedo, kind, iterations=DENOISE_DEFAULTS[
     """The filter's host restatement (wpt_denoise_host): no session, no GPU."""
     return _denoise_planes(lib().wpt_denoise_host, acc, cnt, t, normal, albedo, kind, iterations, sigma_c, sigma_z,
                            flags)
+
+
+DENOISE_RAYS_OUTPUTS = {  # name -> (argument position in wpt_denoise_rays' outputs, dtype, components)
+    "rgb": (0, np.float32, 3), "valid": (1, np.uint8, 1), "rgba": (2, np.uint8, 4), "raw": (3, np.float32, 3),
+    "status": (4, np.uint8, 1),
+}
+
+
+def denoise_rays(rays, width, height, keys=None, sample=0, spp=1, type=1,
+                 iterations=DENOISE_DEFAULTS["iterations"], sigma_c=DENOISE_DEFAULTS["sigma_c"],
+                 sigma_z=DENOISE_DEFAULTS["sigma_z"], flags=DENOISE_DEFAULTS["flags"],
+                 outputs=("rgb", "valid", "rgba", "raw", "status"), device=False):
+    """A filtered width x height frame along a caller's rays (wpt_denoise_rays):
+    rays[y * width + x] is pixel (x, y). A dict of the outputs asked for: `raw`
+    (H, W, 3) f32 and `status` (H, W) u8 are radiance_rays(rays, keys, sample,
+    spp, type); `rgb` (H, W, 3) f32, `valid` (H, W) u8 and `rgba` (H, W, 4) u8
+    are denoise_host() of raw, cnt = spp * status and first_hit_rays()' guide
+    planes of the same rays, all kept on the device. `flags` are the filter's
+    (DENOISE_ALBEDO). device=True: rays (and keys) are contiguous torch tensors
+    on the session's device, and so are the outputs."""
+    n = width * height
+    out, ptr = {}, [None] * 5
+    if device:
+        torch, nr = _device_rays(rays)
+        if nr != n:
+            raise ValueError("rays: width * height rays")
+        if keys is not None and (keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 or not keys.is_contiguous() or keys.numel() != n or keys.device != rays.device):
+            raise ValueError("keys: a contiguous 32-bit integer tensor of one key per ray, on the rays' device")
+        for name in outputs:
+            pos, dt, c = DENOISE_RAYS_OUTPUTS[name]
+            out[name] = torch.empty((height, width) if c == 1 else (height, width, c),
+                                    dtype=torch.float32 if dt is np.float32 else torch.uint8, device=rays.device)
+            ptr[pos] = out[name].data_ptr()
+        _check(lib().wpt_denoise_rays(width, height, rays.data_ptr(), keys.data_ptr() if keys is not None else None,
+                                      sample, spp, type, iterations, sigma_c, sigma_z, flags, RAYS_DEVICE, *ptr))
+        return out
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    if r.shape[0] != n:
+        raise ValueError("rays: width * height rays")
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+    for name in outputs:
+        pos, dt, c = DENOISE_RAYS_OUTPUTS[name]
+        out[name] = np.empty((height, width) if c == 1 else (height, width, c), dtype=dt)
+        ptr[pos] = out[name].ctypes.data
+    _check(lib().wpt_denoise_rays(width, height, r.ctypes.data, None if k is None else k.ctypes.data, sample, spp, type,
+                                  iterations, sigma_c, sigma_z, flags, 0, *ptr))
+    return out
 
 
 REPROJECT_KEEP, REPROJECT_NEAREST, REPROJECT_SAME_SHAPE = 1, 2, 4  # WPT_REPROJECT_*
