@@ -768,6 +768,54 @@ int wpt_radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32
                       uint32_t type, uint32_t flags, float* rgb3, uint8_t* status);
 /* Host only (no session, no GPU): the status rule above on n rays. */
 int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status);
+/* Hemisphere gathers at a caller's points (lightmap texels, probe grids, vertex
+ * irradiance): a point query is a ray query whose ray the device makes, a new
+ * direction for every sample. Record i = {px,py,pz, nx,ny,nz} (24 bytes, the
+ * layout of a ray); the normal is used as given, unit length is the caller's
+ * contract. Key k_i = keys[i], or i if keys is NULL; samples s = sample ..
+ * sample + spp - 1. For (i, s), with the project's f32 operations (wpt_math.h):
+ *   st  = path_seed(frame_seed, k_i, s)
+ *   r1  = xs_next(st); r2 = xs_next(st)      the two jitter draws of a camera path
+ *   ang = (2 * pi) * r1
+ *   WPT_POINTS_COSINE: x = cos(ang) * sqrt(1 - r2), y = sqrt(r2), z = sin(ang) * sqrt(1 - r2)
+ *                      (sample_hemisphere, src/material.rs)
+ *   WPT_POINTS_SPHERE: y = 1 - 2 * r2, q = sqrt(1 - y * y), x = cos(ang) * q, z = sin(ang) * q
+ *                      (uniform over the sphere, the normal its pole: probes in free space)
+ *   xn  = orthogonal(n), zn = cross(n, xn)
+ *   wi  = normalize((xn * x + n * y) + zn * z)
+ *   o   = p + wi * 0.0002                    as a bounce leaves a hit point
+ * and the path is wpt_radiance_rays' path of the ray (o, wi) on the stream st as
+ * it stands (a query path's state after its two discarded draws): throughput
+ * (1,1,1), render type `type`, the session's scene, depth cap, frame seed and
+ * light-debug setting. So always
+ *   rgb3[i] == ((+0 + c_0) + c_1) + ...      (f32, sample order)
+ *   c_j = wpt_radiance_rays(1, wpt_point_rays(record i, k_i, sample + j), &k_i, sample + j, 1, type)
+ * The caller's estimators: irradiance = pi * rgb3 / spp for WPT_POINTS_COSINE,
+ * mean radiance = rgb3 / spp for WPT_POINTS_SPHERE.
+ *  status  u8     wpt_rays_valid's rule on the record's six floats: 1, or 0 for a
+ *                 non-finite component or a normal of three zeros (not traced,
+ *                 rgb3 +0, no path and no ray counted). May be NULL.
+ * A sample whose generated ray (o, wi) fails that rule (only normals far from
+ * unit length give one) is not traced either: it adds +0 and counts no path and
+ * no ray, as the ray query treats that ray; the record's status stays 1.
+ * Everything else is wpt_radiance_rays': a result depends on (record, key,
+ * sample, spp, type, dist), the scene and the render options only; the session
+ * is not touched; the call waits for stock refills as wpt_sync does; wpt_stats
+ * and wpt_kernel_times count its paths and rays as any batch's; flags:
+ * WPT_RAYS_DEVICE: points6, keys, rgb3 and status are device pointers; n == 0
+ * succeeds and launches nothing.
+ * WPT_ERR_INVALID_ARG, with nothing launched and nothing written: n > 0 with a
+ * null points6 or rgb3, spp 0, type > 2, dist > 1, an unknown flag, sample +
+ * spp - 1 > 2^32 - 1, n >= 2^32. The definition to the operation: DESIGN.md §2. */
+#define WPT_POINTS_COSINE 0
+#define WPT_POINTS_SPHERE 1
+int wpt_radiance_points(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                        uint32_t type, uint32_t dist, uint32_t flags, float* rgb3, uint8_t* status);
+/* Host only (no session, no GPU): the ray (o, wi) of every record for ONE sample
+ * index, the same code the kernels run; an invalid record gives six +0. A
+ * generated ray that is itself invalid is given as computed. */
+int wpt_point_rays(size_t n, const float* points6, const uint32_t* keys, uint32_t frame_seed, uint32_t sample,
+                   uint32_t dist, float* rays6);
 /* First-hit feature planes along a caller's rays: wpt_first_hit's planes for
  * rays that are not the session camera's (the guide planes of a fisheye,
  * panorama, orthographic or stereo frame traced through wpt_radiance_rays).

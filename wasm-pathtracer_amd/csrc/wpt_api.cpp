@@ -29,6 +29,7 @@ namespace {
 #include "wpt_guided.h"     // and wpt_sample_map_host's
 #include "wpt_upsample.h"   // and wpt_upsample_host's
 #include "wpt_rays.h"       // the validity rule of a query ray
+#include "wpt_points.h"     // point_ray: the ray of a point query's sample
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -1180,6 +1181,35 @@ int wpt_denoise_rays(uint32_t W, uint32_t H, const float* rays6, const uint32_t*
 int wpt_rays_valid(size_t n, const float* rays6, uint8_t* status) {
   if (n && (!rays6 || !status)) return fail(WPT_ERR_INVALID_ARG, "null argument");
   for (size_t i = 0; i < n; i++) status[i] = ray_valid(rays6 + 6 * i) ? 1 : 0;
+  return WPT_OK;
+}
+
+int wpt_radiance_points(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                        uint32_t type, uint32_t dist, uint32_t flags, float* rgb3, uint8_t* status) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  // radiance_rays' rules on the records, and the distribution
+  if (const char* e = radiance_rays_args(n, points6, sample, spp, type, flags, rgb3)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (dist > WPT_POINTS_SPHERE) return fail(WPT_ERR_INVALID_ARG, "radiance_points: unknown distribution");
+  std::string err;
+  if (!g_session->renderer.radiance_points(n, points6, keys, sample, spp, type, dist, (flags & WPT_RAYS_DEVICE) != 0,
+                                           rgb3, status, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+// point_ray (wpt_points.h) on the host: the generators' own code
+int wpt_point_rays(size_t n, const float* points6, const uint32_t* keys, uint32_t frame_seed, uint32_t sample,
+                   uint32_t dist, float* rays6) {
+  if (n && (!points6 || !rays6)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  if (dist > WPT_POINTS_SPHERE) return fail(WPT_ERR_INVALID_ARG, "point_rays: unknown distribution");
+  for (size_t i = 0; i < n; i++) {
+    V3 o = mk(0.0f, 0.0f, 0.0f), wi = o;
+    uint32_t st = 0;
+    point_ray(points6 + 6 * i, keys ? keys[i] : (uint32_t)i, frame_seed, sample, dist, o, wi, st);
+    float* r = rays6 + 6 * i;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z;
+    r[3] = wi.x; r[4] = wi.y; r[5] = wi.z;
+  }
   return WPT_OK;
 }
 

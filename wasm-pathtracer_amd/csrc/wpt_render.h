@@ -216,7 +216,12 @@ struct RayQuery {
   uint32_t nrays = 0, spp = 1, sample = 0, type = 0;
   float4* acc = nullptr;           // the query's own accumulation (k_accumulate_round's targets)
   uint32_t* cnt = nullptr;
+  // 0: `rays` are the rays. 1 + dist: they are a point query's records {p, n}
+  // (wpt_points.h), the ray of a position made by the generator
+  uint32_t source = 0;
 };
+constexpr int kQueryVariants = 2;
+constexpr int query_variant(bool points) { return points ? 1 : 0; }
 struct Batch {
   enum State { kNew, kBouncing, kCountWait, kIssued };
   // positions k0 .. k0+n-1 of: half h's current round (half >= 0), the
@@ -234,7 +239,8 @@ struct Batch {
   const uint32_t* mlist = nullptr;
   uint32_t nent = 0;
   // a query batch: positions k0 .. k0+n-1 of the rays' chunk (batch_begin then
-  // picks k_generate_rays / k_generate_rays_ps, batch_tail the query's sums)
+  // picks the generator pair of the query's source from kGenQueryTable /
+  // kGenQueryPsTable, batch_tail the query's sums)
   const RayQuery* rq = nullptr;
   bool stock = false;
   bool async = false;
@@ -417,6 +423,11 @@ class Renderer {
   // touched. The caller checks the arguments.
   bool radiance_rays(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
                      bool device, float* rgb3, uint8_t* status, std::string& err);
+  // Hemisphere gathers at a caller's points (wpt_points.h, wpt_radiance_points):
+  // radiance_rays with the records {p, n} as the source and the generators of
+  // dist (kPointsCosine / kPointsSphere) making each position's ray.
+  bool radiance_points(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                       uint32_t type, uint32_t dist, bool device, float* rgb3, uint8_t* status, std::string& err);
   // first_hit's planes along a caller's rays (wpt_first_hit_rays.h,
   // wpt_first_hit_rays): entry i is what first_hit gives a pixel whose primary
   // ray is rays6[i]; status as radiance_rays gives it; a null plane is neither
@@ -826,9 +837,10 @@ class Renderer {
   // The chunks of a query: radiance_rays' body. sums / cnts non-null: the n
   // rays' float4 sums and counts go there (device, entry i = ray i: one frame
   // over all chunks; rays6, keys, rgb3 and status are then device pointers)
-  // and rgb3 may be null: no packed copy is made.
+  // and rgb3 may be null: no packed copy is made. source: RayQuery::source.
   bool query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
-                    bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts, std::string& err);
+                    bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts, std::string& err,
+                    uint32_t source = 0);
   // first_hit_rays' own buffers, kept between calls and freed with first_hit's:
   // the overflow flag, then for host pointers a chunk's rays, planes and status;
   // the traversal-stack spill area of its grid

@@ -2576,6 +2576,8 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 #define WPT_RAYS_KERNELS
 #include "wpt_rays.h"
 #include "wpt_first_hit_rays.h"
+#define WPT_POINTS_KERNELS
+#include "wpt_points.h"
 
 // ===========================================================================
 // Kernel variant tables
@@ -2654,6 +2656,16 @@ struct FirstHitRaysAt {
   static constexpr auto fn = &k_first_hit_rays<V != 0>;
   static constexpr int index = scene_variant(V != 0);
 };
+// a query batch's generators by the query's source: rays, or a point query's records
+template <size_t V>
+struct GenQueryAt {
+  static constexpr auto fn = V ? &k_generate_points : &k_generate_rays;
+  static constexpr int index = query_variant(V != 0);
+};
+template <size_t V>
+struct GenQueryPsAt : GenQueryAt<V> {
+  static constexpr auto fn = V ? &k_generate_points_ps : &k_generate_rays_ps;
+};
 template <size_t V>
 struct PhotonHitAt {
   static constexpr auto fn = &k_photon_hit<V != 0>;
@@ -2673,6 +2685,8 @@ constexpr auto kFinishTable = variant_table<FinishAt>(Variants<kFinishVariants>{
 constexpr auto kGenShadeTable = variant_table<GenShadeAt>(Variants<kSceneVariants>{});
 constexpr auto kFirstHitTable = variant_table<FirstHitAt>(Variants<kSceneVariants>{});
 constexpr auto kFirstHitRaysTable = variant_table<FirstHitRaysAt>(Variants<kSceneVariants>{});
+constexpr auto kGenQueryTable = variant_table<GenQueryAt>(Variants<kQueryVariants>{});
+constexpr auto kGenQueryPsTable = variant_table<GenQueryPsAt>(Variants<kQueryVariants>{});
 constexpr auto kPhotonHitTable = variant_table<PhotonHitAt>(Variants<kSceneVariants>{});
 constexpr auto kPhotonSampleTable = variant_table<PhotonSampleAt>(Variants<kOctVariants>{});
 
@@ -2684,6 +2698,8 @@ static_assert(variant_table_ok<FinishAt>(Variants<kFinishVariants>{}), "k_finish
 static_assert(variant_table_ok<GenShadeAt>(Variants<kSceneVariants>{}), "k_generate_shade's table");
 static_assert(variant_table_ok<FirstHitAt>(Variants<kSceneVariants>{}), "k_first_hit's table");
 static_assert(variant_table_ok<FirstHitRaysAt>(Variants<kSceneVariants>{}), "k_first_hit_rays' table");
+static_assert(variant_table_ok<GenQueryAt>(Variants<kQueryVariants>{}), "the query generators' table");
+static_assert(variant_table_ok<GenQueryPsAt>(Variants<kQueryVariants>{}), "the presolving query generators' table");
 static_assert(variant_table_ok<PhotonHitAt>(Variants<kSceneVariants>{}), "k_photon_hit's table");
 static_assert(variant_table_ok<PhotonSampleAt>(Variants<kOctVariants>{}), "k_photon_sample's table");
 // spot checks in plain words: one entry per family, named by its flags
@@ -2696,6 +2712,8 @@ static_assert(kExtendTable[trav_variant(true, false, 1)] == &k_extend<true, fals
                   kGenShadeTable[scene_variant(true)] == &k_generate_shade<true> &&
                   kFirstHitTable[scene_variant(false)] == &k_first_hit<false> &&
                   kFirstHitRaysTable[scene_variant(true)] == &k_first_hit_rays<true> &&
+                  kGenQueryTable[query_variant(true)] == &k_generate_points &&
+                  kGenQueryPsTable[query_variant(false)] == &k_generate_rays_ps &&
                   kPhotonHitTable[scene_variant(true)] == &k_photon_hit<true> &&
                   kPhotonSampleTable[oct_variant(1)] == &k_photon_sample<1>,
               "the tables' numbering");
@@ -4577,14 +4595,15 @@ bool Renderer::launch_generate(const Batch& B, int i, std::string& err) {
   const uint64_t k0 = B.k0 + B.off[i];
   const uint32_t drop = drop_miss_ ? 1u : 0u;
   if (B.rq) {
+    const int v = query_variant(B.rq->source != 0u);
     const auto launch = [&] {
       if (B.presolve)
-        k_generate_rays_ps<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
-                                                            L.rd[0], L.counts, ds_, L.t, L.id,
-                                                            reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop);
+        kGenQueryPsTable[v]<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
+                                                             L.rd[0], L.counts, ds_, L.t, L.id,
+                                                             reinterpret_cast<uint32_t*>(L.res_ctr(0)), drop);
       else
-        k_generate_rays<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
-                                                         L.rd[0], L.counts);
+        kGenQueryTable[v]<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, k0, nn, L.pixel, L.thr[0], L.col, L.ro[0],
+                                                           L.rd[0], L.counts);
     };
     return launch_timed(C, 0, launch, err);
   }
@@ -5693,11 +5712,17 @@ bool Renderer::radiance_rays(size_t n, const float* rays6, const uint32_t* keys,
   return query_chunks(n, rays6, keys, sample, spp, type, device, rgb3, status, nullptr, nullptr, err);
 }
 
+bool Renderer::radiance_points(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                               uint32_t type, uint32_t dist, bool device, float* rgb3, uint8_t* status,
+                               std::string& err) {
+  return query_chunks(n, points6, keys, sample, spp, type, device, rgb3, status, nullptr, nullptr, err, 1u + dist);
+}
+
 // sums: the chunk at c0 adds to entries c0 .. of the caller's frame (denoise_rays)
 // and takes nothing of d_query_.
 bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
                             uint32_t type, bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts,
-                            std::string& err) {
+                            std::string& err, uint32_t source) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   // refills and fill batches in flight use the lanes this call may resize
@@ -5738,6 +5763,7 @@ bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, 
     R.spp = spp;
     R.sample = sample;
     R.type = type;
+    R.source = source;
     if (sums) {
       HIP_OK(hipMemsetAsync(R.acc, 0, sizeof(float4) * cn, stream_));
       HIP_OK(hipMemsetAsync(R.cnt, 0, sizeof(uint32_t) * cn, stream_));

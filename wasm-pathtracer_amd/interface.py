@@ -501,6 +501,56 @@ def radiance_rays(rays, keys=None, sample=0, spp=1, type=1, device=False):
     return rgb, status
 
 
+POINTS_COSINE = 0  # WPT_POINTS_COSINE: cosine-weighted about the normal (irradiance = pi * rgb / spp)
+POINTS_SPHERE = 1  # WPT_POINTS_SPHERE: uniform over the sphere (mean radiance = rgb / spp)
+
+
+def radiance_points(points, keys=None, sample=0, spp=1, type=1, dist=POINTS_COSINE, device=False):
+    """Hemisphere gathers at a caller's points (wpt_radiance_points): record i =
+    points[i] = {position, normal}; sample s of it leaves the point along a
+    direction drawn on the device about the normal (dist: POINTS_COSINE or
+    POINTS_SPHERE) and is then radiance_rays' path of that ray. Returns (rgb
+    (n, 3) f32: the sum over the record's samples in sample order, status (n,)
+    u8: 0 for a record with a non-finite component or a zero normal). keys,
+    device and the session: as radiance_rays."""
+    if device:
+        import torch
+
+        if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 6:
+            raise ValueError("points: a contiguous float32 tensor of 6 components per record")
+        n = points.numel() // 6
+        if keys is not None and (keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 or not keys.is_contiguous()
+                                 or keys.numel() != n or keys.device != points.device):
+            raise ValueError("keys: a contiguous 32-bit integer tensor of one key per record, on the points' device")
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=points.device)
+        _check(lib().wpt_radiance_points(n, points.data_ptr(), keys.data_ptr() if keys is not None else None, sample,
+                                         spp, type, dist, RAYS_DEVICE, rgb.data_ptr(), status.data_ptr()))
+        return rgb, status
+    r = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+    rgb = np.empty((n, 3), dtype=np.float32)
+    status = np.empty(n, dtype=np.uint8)
+    _check(lib().wpt_radiance_points(n, r.ctypes.data, None if k is None else k.ctypes.data, sample, spp, type, dist, 0,
+                                     rgb.ctypes.data, status.ctypes.data))
+    return rgb, status
+
+
+def point_rays(points, keys=None, seed=0xBABABEBE, sample=0, dist=POINTS_COSINE):
+    """The ray radiance_points makes for sample `sample` of every record
+    (wpt_point_rays; host only, no session): (n, 6) f32 {origin, direction}, six
+    +0 for an invalid record."""
+    r = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+    rays = np.empty((n, 6), dtype=np.float32)
+    _check(lib().wpt_point_rays(n, r.ctypes.data, None if k is None else k.ctypes.data, seed, sample, dist,
+                                rays.ctypes.data))
+    return rays
+
+
 def rays_valid(rays):
     """The status radiance_rays gives each ray (wpt_rays_valid; host only, no
     session): 1 if its six components are finite and its direction is not three
