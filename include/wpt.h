@@ -816,6 +816,45 @@ int wpt_radiance_points(size_t n, const float* points6, const uint32_t* keys, ui
  * generated ray that is itself invalid is given as computed. */
 int wpt_point_rays(size_t n, const float* points6, const uint32_t* keys, uint32_t frame_seed, uint32_t sample,
                    uint32_t dist, float* rays6);
+/* Spherical-harmonic projection of a point's gathers (probe grids): the samples
+ * of wpt_radiance_points, each weighted by the real SH basis of its own
+ * direction. Records, keys, samples, type, dist, status and flags are
+ * wpt_radiance_points'. nc = (order + 1)^2 coefficients, order 0 .. 2. With
+ *   (o_j, w_j) = wpt_point_rays(record i, k_i, sample + j)
+ *   c_j        = wpt_radiance_rays(1, (o_j, w_j), &k_i, sample + j, 1, type)
+ * always
+ *   sh[(i * nc + k) * 3 + ch] == ((+0 + Y_k(w_0) * c_0.ch) + Y_k(w_1) * c_1.ch) + ...
+ * in f32, in sample order, one rounding per product and per addition. The
+ * basis (wpt_sh_basis): world axes, z the polar axis, no Condon-Shortley sign,
+ * the direction (x, y, z) used as given, each operation one f32 rounding:
+ *   Y0 = C0
+ *   Y1 = C1 * y          Y2 = C1 * z          Y3 = C1 * x
+ *   Y4 = C2 * (x * y)    Y5 = C2 * (y * z)    Y7 = C2 * (x * z)
+ *   Y6 = C3 * ((3 * (z * z)) - 1)
+ *   Y8 = C4 * ((x * x) - (y * y))
+ * C0 .. C4 the f32 nearest to sqrt(1 / 4pi), sqrt(3 / 4pi), sqrt(15 / 4pi),
+ * sqrt(5 / 16pi), sqrt(15 / 16pi). The coefficients of a lower order are the
+ * leading coefficients of a higher order, bit for bit.
+ * A sample that is not traced (an invalid record, or an invalid generated ray)
+ * adds nothing to any coefficient; an invalid record's row is all +0.
+ * The caller's estimators: for WPT_POINTS_SPHERE, 4 pi / spp * sh estimates the
+ * SH coefficients of the incoming radiance; for WPT_POINTS_COSINE, pi / spp * sh
+ * those of the radiance times the cosine about the normal.
+ * Everything else is wpt_radiance_points': a result depends on (record, key,
+ * sample, spp, type, dist, order), the scene and the render options only (not on
+ * WPT_SH_CHUNK, the records one internal pass takes); the session is not touched;
+ * stock refills, wpt_stats, wpt_kernel_times, WPT_RAYS_DEVICE and n == 0 as there.
+ * WPT_ERR_INVALID_ARG, with nothing launched and nothing written: that call's
+ * cases with sh in place of rgb3, and order > WPT_SH_MAX_ORDER. The definition
+ * to the operation: DESIGN.md §2. */
+#define WPT_SH_MAX_ORDER 2
+#define WPT_SH_CHUNK 262144
+int wpt_probe_sh(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                 uint32_t type, uint32_t dist, uint32_t order, uint32_t flags, float* sh, uint8_t* status);
+/* Host only (no session, no GPU): the (order + 1)^2 basis values of each of n
+ * directions {x, y, z}, the same code the kernel runs. WPT_ERR_INVALID_ARG for
+ * a null pointer with n > 0 or order > WPT_SH_MAX_ORDER. */
+int wpt_sh_basis(size_t n, const float* dirs3, uint32_t order, float* out);
 /* First-hit feature planes along a caller's rays: wpt_first_hit's planes for
  * rays that are not the session camera's (the guide planes of a fisheye,
  * panorama, orthographic or stereo frame traced through wpt_radiance_rays).

@@ -85,6 +85,8 @@ _SIGS = {
     "wpt_rays_valid": (ctypes.c_int, [c_sz, c_p, c_p]),
     "wpt_radiance_points": (ctypes.c_int, [c_sz, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
     "wpt_point_rays": (ctypes.c_int, [c_sz, c_p, c_p, c_u32, c_u32, c_u32, c_p]),
+    "wpt_probe_sh": (ctypes.c_int, [c_sz, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32, c_p, c_p]),
+    "wpt_sh_basis": (ctypes.c_int, [c_sz, c_p, c_u32, c_p]),
     "wpt_first_hit_rays": (ctypes.c_int, [c_sz, c_p, c_u32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "wpt_denoise_rays": (ctypes.c_int, [c_u32, c_u32, c_p, c_p, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_u32, c_u32,
                                         c_p, c_p, c_p, c_p, c_p]),

@@ -30,6 +30,7 @@ namespace {
 #include "wpt_upsample.h"   // and wpt_upsample_host's
 #include "wpt_rays.h"       // the validity rule of a query ray
 #include "wpt_points.h"     // point_ray: the ray of a point query's sample
+#include "wpt_sh.h"         // sh_basis: the weights of an SH query's samples
 
 struct Session {
   std::map<uint32_t, std::vector<float>> preload;   // Mesh::Preload (mesh.rs:8-13)
@@ -1210,6 +1211,30 @@ int wpt_point_rays(size_t n, const float* points6, const uint32_t* keys, uint32_
     r[0] = o.x; r[1] = o.y; r[2] = o.z;
     r[3] = wi.x; r[4] = wi.y; r[5] = wi.z;
   }
+  return WPT_OK;
+}
+
+static_assert(WPT_SH_MAX_ORDER == kShMaxOrder && WPT_SH_CHUNK == kShQueryChunk, "the header's SH constants");
+
+int wpt_probe_sh(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
+                 uint32_t dist, uint32_t order, uint32_t flags, float* sh, uint8_t* status) {
+  if (!g_session) return fail(WPT_ERR_NOT_INIT, "init not called");
+  // radiance_points' rules, and the order
+  if (const char* e = radiance_rays_args(n, points6, sample, spp, type, flags, sh)) return fail(WPT_ERR_INVALID_ARG, e);
+  if (dist > WPT_POINTS_SPHERE) return fail(WPT_ERR_INVALID_ARG, "probe_sh: unknown distribution");
+  if (order > WPT_SH_MAX_ORDER) return fail(WPT_ERR_INVALID_ARG, "probe_sh: order above WPT_SH_MAX_ORDER");
+  std::string err;
+  if (!g_session->renderer.probe_sh(n, points6, keys, sample, spp, type, dist, order, (flags & WPT_RAYS_DEVICE) != 0, sh,
+                                    status, err))
+    return fail(WPT_ERR_DEVICE, err);
+  return WPT_OK;
+}
+
+// sh_basis (wpt_sh.h) on the host: the kernel's own code
+int wpt_sh_basis(size_t n, const float* dirs3, uint32_t order, float* out) {
+  if (n && (!dirs3 || !out)) return fail(WPT_ERR_INVALID_ARG, "null argument");
+  if (order > WPT_SH_MAX_ORDER) return fail(WPT_ERR_INVALID_ARG, "sh_basis: order above WPT_SH_MAX_ORDER");
+  sh_basis_rows(n, dirs3, order, out);
   return WPT_OK;
 }
 

@@ -185,6 +185,7 @@ struct PathSet {
   DevBuf<uint32_t> counts;    // kCountWords, see above
   PinBuf<uint32_t> h_counts;  // pinned mirror
   DevBuf<uint2> spill;        // traversal-stack spill (entries beyond the LDS slots), spill.cap() entries
+  DevBuf<float4> shdir;       // per path: {direction, traced} (k_sh_dirs); grown by SH queries only
   float* hit_t(int k) const { return k ? t1 : t; }
   int32_t* hit_id(int k) const { return k ? id1 : id; }
   // count words: rays of bounce b, shadow rays of bounce b, k_shade's append
@@ -214,12 +215,24 @@ struct RayQuery {
   const uint32_t* keys = nullptr;  // per ray, or null: key0 + ray
   uint32_t key0 = 0;
   uint32_t nrays = 0, spp = 1, sample = 0, type = 0;
-  float4* acc = nullptr;           // the query's own accumulation (k_accumulate_round's targets)
+  // the query's own accumulation: k_accumulate_round's targets, or for an SH
+  // query (sh_nc != 0, wpt_sh.h) the per-record sums, 3 * sh_nc f32 each at entry
+  // `ray`, that k_accumulate_sh adds to (cnt is then unused). One slot, so that
+  // the struct the generators take by value keeps its size and offsets.
+  union {
+    float4* acc = nullptr;
+    float* sh;
+  };
   uint32_t* cnt = nullptr;
   // 0: `rays` are the rays. 1 + dist: they are a point query's records {p, n}
   // (wpt_points.h), the ray of a position made by the generator
   uint32_t source = 0;
+  uint32_t sh_nc = 0;  // an SH query: its (order + 1)^2 coefficients per record; else 0 (in the tail padding)
 };
+static_assert(sizeof(RayQuery) == 64, "the generators' kernarg layout");
+// the records of one chunk of an SH query (WPT_SH_CHUNK): its sums are 12 * nc
+// bytes per record (108 at order 2) where a ray query's are 20, so 2^18, not 2^21
+constexpr size_t kShQueryChunk = (size_t)1 << 18;
 constexpr int kQueryVariants = 2;
 constexpr int query_variant(bool points) { return points ? 1 : 0; }
 struct Batch {
@@ -428,6 +441,11 @@ class Renderer {
   // dist (kPointsCosine / kPointsSphere) making each position's ray.
   bool radiance_points(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
                        uint32_t type, uint32_t dist, bool device, float* rgb3, uint8_t* status, std::string& err);
+  // SH projection of a point's gathers (wpt_sh.h, wpt_probe_sh): radiance_points
+  // whose samples are weighted by the SH basis of their own directions; sh holds
+  // 3 * (order + 1)^2 f32 per record.
+  bool probe_sh(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
+                uint32_t dist, uint32_t order, bool device, float* sh, uint8_t* status, std::string& err);
   // first_hit's planes along a caller's rays (wpt_first_hit_rays.h,
   // wpt_first_hit_rays): entry i is what first_hit gives a pixel whose primary
   // ray is rays6[i]; status as radiance_rays gives it; a null plane is neither
@@ -838,9 +856,11 @@ class Renderer {
   // rays' float4 sums and counts go there (device, entry i = ray i: one frame
   // over all chunks; rays6, keys, rgb3 and status are then device pointers)
   // and rgb3 may be null: no packed copy is made. source: RayQuery::source.
+  // sh_nc > 0: an SH query of that many coefficients (chunks of kShQueryChunk
+  // records); rgb3 is then its output, 3 * sh_nc f32 per record.
   bool query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp, uint32_t type,
                     bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts, std::string& err,
-                    uint32_t source = 0);
+                    uint32_t source = 0, uint32_t sh_nc = 0);
   // first_hit_rays' own buffers, kept between calls and freed with first_hit's:
   // the overflow flag, then for host pointers a chunk's rays, planes and status;
   // the traversal-stack spill area of its grid

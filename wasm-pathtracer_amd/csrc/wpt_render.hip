@@ -2578,6 +2578,8 @@ inline void pack_shadow_rays(size_t n, const float* pq, const int32_t* light, st
 #include "wpt_first_hit_rays.h"
 #define WPT_POINTS_KERNELS
 #include "wpt_points.h"
+#define WPT_SH_KERNELS
+#include "wpt_sh.h"
 
 // ===========================================================================
 // Kernel variant tables
@@ -2931,6 +2933,7 @@ void Renderer::free_lane_paths(PathSet& L) {
   L.so.reset();
   L.sd.reset();
   L.sc.reset();
+  L.shdir.reset();
   L.cap = 0;
 }
 
@@ -3754,7 +3757,13 @@ bool Renderer::batch_tail(Batch& B, std::string& err) {
     if (B.stock)
       k_stock_store<<<blocks_for(nn), kBlock, 0, s>>>(L.pixel, nn, L.col, d_stock_);
     else if (!launch_timed(C, 4, [&] {
-               if (round)
+               if (B.rq && B.rq->sh_nc) {
+                 // an SH query (wpt_sh.h): the slice's directions again, then the weighted sums
+                 const uint32_t nc = B.rq->sh_nc;
+                 k_sh_dirs<<<blocks_for(nn), kBlock, 0, s>>>(*B.rq, seed_, B.k0 + B.off[i], nn, L.shdir);
+                 k_accumulate_sh<<<blocks_for((uint64_t)nn * nc), kBlock, 0, s>>>(nn, nc, L.pixel, L.col, L.shdir,
+                                                                                B.rq->sh);
+               } else if (round)
                  k_accumulate_round<<<blocks_for(nn), kBlock, 0, s>>>(part, nn, L.pixel, L.col, acc, cnt);
                else
                  k_accumulate<<<blocks_for(std::min<uint64_t>(nn, npix)), kBlock, 0, s>>>(
@@ -5688,18 +5697,22 @@ bool Renderer::compute_map(const uint32_t* count, bool& invalid, std::string& er
 // next_path_ are not touched, the frame is not read.
 namespace {
 constexpr size_t kQueryChunk = (size_t)1 << 21;  // a 1080p frame's rays are one chunk
+// nc > 0: an SH query, whose sums are 3 * nc f32 per record in the caller's
+// layout: no float4 sums, no counts, and no packed copy (the result is copied
+// from the sums as they lie)
 struct QueryLayout {
-  size_t acc, cnt, sums_end, rays, keys, rgb, status, bytes;
-  constexpr QueryLayout(size_t n, bool host, bool keyed)
-      : acc(0), cnt(0), sums_end(0), rays(0), keys(0), rgb(0), status(0), bytes(0) {
+  size_t acc, cnt, sh, sums_end, rays, keys, rgb, status, bytes;
+  constexpr QueryLayout(size_t n, bool host, bool keyed, uint32_t nc = 0)
+      : acc(0), cnt(0), sh(0), sums_end(0), rays(0), keys(0), rgb(0), status(0), bytes(0) {
     Slices s;
-    acc = s.take(sizeof(float4) * n);
-    cnt = s.take(sizeof(uint32_t) * n);
+    acc = s.take(nc ? 0 : sizeof(float4) * n);
+    cnt = s.take(nc ? 0 : sizeof(uint32_t) * n);
+    sh = s.take(3 * sizeof(float) * nc * n);
     sums_end = s.at;
     if (host) {
       rays = s.take(6 * sizeof(float) * n);
       keys = s.take(keyed ? sizeof(uint32_t) * n : 0);
-      rgb = s.take(3 * sizeof(float) * n);
+      rgb = s.take(nc ? 0 : 3 * sizeof(float) * n);
       status = s.take(n);
     }
     bytes = s.at;
@@ -5718,27 +5731,38 @@ bool Renderer::radiance_points(size_t n, const float* points6, const uint32_t* k
   return query_chunks(n, points6, keys, sample, spp, type, device, rgb3, status, nullptr, nullptr, err, 1u + dist);
 }
 
+bool Renderer::probe_sh(size_t n, const float* points6, const uint32_t* keys, uint32_t sample, uint32_t spp,
+                        uint32_t type, uint32_t dist, uint32_t order, bool device, float* sh, uint8_t* status,
+                        std::string& err) {
+  return query_chunks(n, points6, keys, sample, spp, type, device, sh, status, nullptr, nullptr, err, 1u + dist,
+                      sh_coeffs(order));
+}
+
 // sums: the chunk at c0 adds to entries c0 .. of the caller's frame (denoise_rays)
 // and takes nothing of d_query_.
 bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, uint32_t sample, uint32_t spp,
                             uint32_t type, bool device, float* rgb3, uint8_t* status, float4* sums, uint32_t* cnts,
-                            std::string& err, uint32_t source) {
+                            std::string& err, uint32_t source, uint32_t sh_nc) {
   if (!scene_ok_) { err = "no scene"; return false; }
   if (n == 0) return true;
   // refills and fill batches in flight use the lanes this call may resize
   if (!sync(err)) return false;
   if (type == 2u && !build_photons(err)) return false;
   const uint64_t bsz = std::min<uint64_t>(std::max<uint64_t>(batch_, 1), 0xFFFFFFFFull);
-  for (size_t c0 = 0; c0 < n; c0 += kQueryChunk) {
-    const size_t cn = std::min(kQueryChunk, n - c0);
+  const size_t chunk = sh_nc ? kShQueryChunk : kQueryChunk;
+  const size_t rgbw = sh_nc ? 3 * (size_t)sh_nc : 3;  // f32 per record of the result
+  for (size_t c0 = 0; c0 < n; c0 += chunk) {
+    const size_t cn = std::min(chunk, n - c0);
     const uint32_t cnn = (uint32_t)cn;
-    const QueryLayout Q(cn, !device, keys != nullptr);
+    const QueryLayout Q(cn, !device, keys != nullptr, sh_nc);
     if (!sums) HIP_OK(d_query_.grow(Q.bytes));
     char* m = d_query_;
     RayQuery R;
     R.acc = sums ? sums + c0 : (float4*)(m + Q.acc);
     R.cnt = sums ? cnts + c0 : (uint32_t*)(m + Q.cnt);
-    float* d_rgb = rgb3 ? rgb3 + 3 * c0 : nullptr;
+    if (sh_nc) R.sh = (float*)(m + Q.sh);
+    R.sh_nc = sh_nc;
+    float* d_rgb = rgb3 ? rgb3 + rgbw * c0 : nullptr;
     uint8_t* d_status = status ? status + c0 : nullptr;
     char* hp = nullptr;
     if (device) {
@@ -5780,8 +5804,10 @@ bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, 
       const int ml = main_lanes();
       const uint64_t want = std::min(bsz, total);
       const uint64_t per = (want + ml - 1) / ml;
-      for (int i = 0; i < ml; i++)
+      for (int i = 0; i < ml; i++) {
         if (!ensure_lane(i, (i == 0 && want < (uint64_t)ml * kMinLanePaths) ? want : per, err)) return false;
+        if (sh_nc) HIP_OK(lanes_[i].shdir.grow(lanes_[i].cap));  // (no launch of this call is out yet)
+      }
     }
     Batch M;
     M.rq = &R;
@@ -5789,17 +5815,28 @@ bool Renderer::query_chunks(size_t n, const float* rays6, const uint32_t* keys, 
     for (uint64_t k0 = 0; k0 < total; k0 += cap)
       if (!run_batch(k0, std::min<uint64_t>(cap, total - k0), -1, err, nullptr, 0, &M)) return false;
     // (the main stream has waited for every lane's accumulation: batch_tail)
-    if (d_rgb) {
-      k_rays_unpack<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.acc, d_rgb);
-      HIP_OK(hipGetLastError());
-    }
-    if (!device) {
-      const size_t back = (status ? Q.status + cn : Q.rgb + 3 * sizeof(float) * cn) - Q.rgb;
-      HIP_OK(hipMemcpyAsync(hp + Q.rgb, m + Q.rgb, back, hipMemcpyDeviceToHost, stream_));
+    if (sh_nc) {
+      // the sums are the result as they lie
+      const size_t bytes = sizeof(float) * rgbw * cn;
+      if (device) {
+        HIP_OK(hipMemcpyAsync(d_rgb, R.sh, bytes, hipMemcpyDeviceToDevice, stream_));
+      } else {
+        HIP_OK(hipMemcpyAsync(rgb3 + rgbw * c0, R.sh, bytes, hipMemcpyDeviceToHost, stream_));
+        if (status) HIP_OK(hipMemcpyAsync(hp + Q.status, m + Q.status, cn, hipMemcpyDeviceToHost, stream_));
+      }
+    } else {
+      if (d_rgb) {
+        k_rays_unpack<<<blocks_for(cnn), kBlock, 0, stream_>>>(cnn, R.acc, d_rgb);
+        HIP_OK(hipGetLastError());
+      }
+      if (!device) {
+        const size_t back = (status ? Q.status + cn : Q.rgb + 3 * sizeof(float) * cn) - Q.rgb;
+        HIP_OK(hipMemcpyAsync(hp + Q.rgb, m + Q.rgb, back, hipMemcpyDeviceToHost, stream_));
+      }
     }
     HIP_OK(hipStreamSynchronize(stream_));
     if (!device) {
-      memcpy(rgb3 + 3 * c0, hp + Q.rgb, 3 * sizeof(float) * cn);
+      if (!sh_nc) memcpy(rgb3 + 3 * c0, hp + Q.rgb, 3 * sizeof(float) * cn);
       if (status) memcpy(status + c0, hp + Q.status, cn);
     }
   }

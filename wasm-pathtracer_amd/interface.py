@@ -551,6 +551,54 @@ def point_rays(points, keys=None, seed=0xBABABEBE, sample=0, dist=POINTS_COSINE)
     return rays
 
 
+SH_MAX_ORDER = 2  # WPT_SH_MAX_ORDER
+SH_CHUNK = 1 << 18  # WPT_SH_CHUNK: the records one internal pass of probe_sh takes (no result depends on it)
+
+
+def probe_sh(points, keys=None, sample=0, spp=1, type=1, dist=POINTS_SPHERE, order=SH_MAX_ORDER, device=False):
+    """Spherical-harmonic projection of a point's gathers (wpt_probe_sh):
+    radiance_points' samples, each weighted by the real SH basis (sh_basis) of
+    its own direction. Returns (sh (n, (order + 1)^2, 3) f32: per coefficient
+    the sum over the record's traced samples in sample order, status (n,) u8 as
+    radiance_points gives it). 4 pi / spp * sh (POINTS_SPHERE) estimates the
+    radiance's SH coefficients. keys, device and the session: as radiance_rays."""
+    nc = (order + 1) ** 2 if 0 <= order <= SH_MAX_ORDER else 1  # (the call rejects the order)
+    if device:
+        import torch
+
+        if points.dtype != torch.float32 or not points.is_contiguous() or points.numel() % 6:
+            raise ValueError("points: a contiguous float32 tensor of 6 components per record")
+        n = points.numel() // 6
+        if keys is not None and (keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                                 or not keys.is_contiguous()
+                                 or keys.numel() != n or keys.device != points.device):
+            raise ValueError("keys: a contiguous 32-bit integer tensor of one key per record, on the points' device")
+        sh = torch.empty((n, nc, 3), dtype=torch.float32, device=points.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=points.device)
+        _check(lib().wpt_probe_sh(n, points.data_ptr(), keys.data_ptr() if keys is not None else None, sample, spp,
+                                  type, dist, order, RAYS_DEVICE, sh.data_ptr(), status.data_ptr()))
+        return sh, status
+    r = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    n = r.shape[0]
+    k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(n)
+    sh = np.empty((n, nc, 3), dtype=np.float32)
+    status = np.empty(n, dtype=np.uint8)
+    _check(lib().wpt_probe_sh(n, r.ctypes.data, None if k is None else k.ctypes.data, sample, spp, type, dist, order, 0,
+                              sh.ctypes.data, status.ctypes.data))
+    return sh, status
+
+
+def sh_basis(dirs, order=SH_MAX_ORDER):
+    """The real SH basis probe_sh weights a sample with (wpt_sh_basis; host only,
+    no session): (n, (order + 1)^2) f32 for directions (n, 3), used as given.
+    World axes, z the polar axis, no Condon-Shortley sign."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n = d.shape[0]
+    out = np.empty((n, (order + 1) ** 2 if 0 <= order <= SH_MAX_ORDER else 1), dtype=np.float32)
+    _check(lib().wpt_sh_basis(n, d.ctypes.data, order, out.ctypes.data))
+    return out
+
+
 def rays_valid(rays):
     """The status radiance_rays gives each ray (wpt_rays_valid; host only, no
     session): 1 if its six components are finite and its direction is not three
